@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark: Msamples/s of the MI355X path tracer on BASELINE.json configs[1].
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (rate, ms_per_step,
+the configuration, the image's mean, the device).  `--dump-outputs DIR` also writes the image the
+last timed step left in the accumulator (what a caller of the timed path receives) as
+DIR/accum.npy, float32 (H, W, 3), radiance sums over the step's spp.  `--full` adds every other
+measurement described below (extra steps, the roofline, the reference's call loop, the CPU
+baseline and the MSE against it); without it none of them runs.
 
 Workload (configs[1]): the synthetic Diffuse sphere-in-box scene (34,570 triangles,
 Lambert mode, Scene1 camera and 4 point lights), 1920x1080, depth 8.  One STEP = one
@@ -11,12 +18,13 @@ Lambert mode, Scene1 camera and 4 point lights), 1920x1080, depth 8.  One STEP =
 sharding), every rank renders its share into a device fp32 accumulator, and
 the accumulators are summed to rank 0 with one RCCL reduce (torch.distributed "nccl" = RCCL
 over xGMI).  The image is fixed as N grows ("strong" scaling, north_star's 1 -> 8 GPU scaling
-of the 1024-spp image); value = the step's samples / max-over-ranks wall time.  At N > 1 one
-more step with 1024 frames per rank reports the weak-scaling rate as `value_weak`.
+of the 1024-spp image); value = the step's samples / max-over-ranks wall time.  With --full, at
+N > 1 one more step with 1024 frames per rank reports the weak-scaling rate as `value_weak`.
 
 `--config 3|4d|4l|5` runs BASELINE.json's other configs through the same harness (4d/4l: 4096
 spp per step); the driver's default run is configs[1].
 
+The fields below are those a --full run adds to the result line.
 Extra fields: `roofline` (HBM roofline of the mode's dominant kernel, measured with one HIP event
 pair per launch on the stream it runs on, per kernel: in the Lambert / Conductor / Dielectric modes
 k_trace_pair (the shadow rays of bounce b and the extension rays of b+1 of a batch of --frames-per-launch frames, 128 by default), 48
@@ -117,6 +125,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the extra steps (primary dedup off, single "
+                         "stream, the other scaling mode), the traversal-statistics render and the roofline, the "
+                         "reference's call loop, the CPU baseline and the MSE against it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the last timed step (rank 0, after the reduce) as DIR/accum.npy")
     ap.add_argument("--config", default="2", choices=sorted(CONFIGS),
                     help="BASELINE.json config: 2 = configs[1] (default, the headline), 3, 4d, 4l, 5, 5t")
     ap.add_argument("--scene-source", choices=["auto", "procedural", "glb"], default="auto",
@@ -130,9 +144,9 @@ def parse():
     ap.add_argument("--kernel", type=int, default=2, help="0 = megakernel, 1 = wavefront, 2 = auto")
     ap.add_argument("--frames-per-launch", type=int, default=128)
     ap.add_argument("--no-dedup-check", action="store_true",
-                    help="skip the extra step timed with pt_set_primary_dedup(0)")
+                    help="--full: skip the extra steps timed with pt_set_primary_dedup(0) and on a single stream")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the MSE")
     ap.add_argument("--traffic-json", default=str(ROOT / "profiles" / "traffic.json"),
                     help="PMC traffic per launch measured by tools/profile.sh (optional)")
     ap.add_argument("--queue-budget", type=int, default=0,
@@ -147,7 +161,7 @@ def parse():
     ap.add_argument("--reference-loops", type=int, default=1024,
                     help="pt_render calls (1 spp each, frame.id++, 24.9 MB download per call: the reference's "
                          "OptixView::DrawOptix -> OptixRenderer::Render loop, here the 1024 samples of the "
-                         "configs[1] image) timed for value_reference_loop; 0 = off")
+                         "configs[1] image) timed for value_reference_loop with --full; 0 = off")
     a = ap.parse_args()
     scene, spp, scaling, a.workload = CONFIGS[a.config]
     a.scaling = a.scaling or scaling
@@ -288,8 +302,13 @@ def main():
     # Transparency: the same step with every frame's (identical) camera ray traced again
     # instead of once per pixel per batch (pt_set_primary_dedup; bit-identical images).
     img = accum.cpu().numpy() if rank == 0 else None  # the timed steps' image
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's accumulator (each step clears it): what the timed path hands its
+        # caller, 24.9 MB at 1920x1080; frame ids and scene are fixed by the arguments
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "accum.npy"), img)
     value_nodedup = None
-    if args.kernel != 0 and not args.no_dedup_check:
+    if args.full and args.kernel != 0 and not args.no_dedup_check:
         r.set_primary_dedup(False)
         if dist is not None:
             dist.barrier()
@@ -309,7 +328,7 @@ def main():
     # Transparency at N > 1: the other scaling mode's rate from one more step (weak: every rank
     # renders the step's full spp; strong: the ranks split it)
     value_other = None
-    if world > 1:
+    if args.full and world > 1:
         other = "weak" if args.scaling == "strong" else "strong"
         dist.barrier()
         torch.cuda.synchronize(dev)
@@ -326,7 +345,7 @@ def main():
     # kernel instance): node visits (global / from LDS), triangle tests and rays per trace launch,
     # for the vector-memory roofline of the trace kernels (roofline.vmem).  Its time is not used.
     trav = None
-    if args.kernel != 0:
+    if args.full and args.kernel != 0:
         r.set_traversal_stats(True)
         r.stats_reset()
         r.accum_clear()
@@ -343,7 +362,7 @@ def main():
     # (roofline.single_stream); on one stream the timed region is that run.
     single = None
     s1_all_ms = None  # single-stream mean over all trace launches (vmem rate)
-    if args.kernel != 0 and not args.no_dedup_check and eff_streams > 1:
+    if args.full and args.kernel != 0 and not args.no_dedup_check and eff_streams > 1:
         r.set_wavefront_streams(1)
         r.stats_reset()
         if dist is not None:
@@ -374,6 +393,56 @@ def main():
         r.set_wavefront_streams(args.wavefront_streams)
     if rank == 0:
         nan_px = int(np.isnan(img).any(axis=-1).sum())
+        # the result line of a plain run; --full adds its measurements below
+        out = {
+            "metric": "Msamples/sec at 1920x1080, max-depth 8; MSE vs reference",
+            "value": round(value, 3),
+            "unit": "Msamples/sec",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 2),
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": f"synthetic (procedural {args.scene} scene; the reference's glTF assets are not in its repo)",
+            "config": {
+                "workload": args.workload + (f", {world}xMI355X" if args.scaling == "strong" or world == 1
+                                             else f" per GPU, spp-sharded over {world} GPUs + RCCL reduce"),
+                "scene": args.scene,
+                "triangles": scene.n_triangles,
+                "width": args.width,
+                "height": args.height,
+                "spp_per_step": args.spp,
+                "spp_per_gpu_per_step": args.spp if args.scaling == "weak" else round(args.spp / world, 2),
+                "max_depth": args.depth,
+                "material_mode": {0: "default", 1: "lambert", 2: "conductor", 3: "dielectric",
+                                  4: "layered"}.get(scene.material_mode, str(scene.material_mode)),
+                "kernel": {0: "megakernel", 1: "wavefront", 2: "auto (wavefront)"}[args.kernel],
+                "frames_per_launch": args.frames_per_launch,
+                "wavefront_streams": eff_streams,
+                "parallelism": f"spp-shard x{world}",
+                "scene_source": source,
+                # the batches the timed region ran (pt_stats): frames per batch after the queue
+                # budget (pt_set_queue_budget, default a quarter of the device memory) and the
+                # device memory the wavefront queues held
+                "batch_frames": st["last_batch_frames"],
+                "queue_bytes": st["queue_bytes"],
+                "queue_budget_bytes": st["queue_budget"],
+                "bvh_build_ms": round(bvh_ms, 3),  # the first build in the process (code loading included)
+                # pt_options.bvh_builder = PT_BVH_AUTO: the binned-SAH binary tree built on the GPU
+                # (pt_sah_gpu.hip) and collapsed to BVH4 on the GPU; the time above covers both
+                "bvh_builder": "auto (GPU binned SAH + GPU SAH-optimal BVH4 collapse)",
+                "primary_dedup": args.kernel != 0,
+            },
+            "full": args.full,
+            "image": {"mean": float(np.nanmean(img) / per_step_spp), "nan_pixels": nan_px},
+            # what the process group ran: backend ("nccl" = RCCL), ranks, reduce time per step
+            "distributed": distributed,
+            "device": device_identity(torch, local_rank),
+        }
+    if rank == 0 and args.full:
         kernel_s = st["total_render_ms"] / 1e3
         alg_bytes = st["segments"] * BYTES_PER_SEGMENT + st["samples"] * BYTES_PER_SAMPLE
         fused = scene.material_mode in (1, 2, 3)
@@ -529,48 +598,7 @@ def main():
                        "issue_frac": vl.get("issue_frac"), "lane_utilisation": vl.get("lane_utilisation")}
         else:
             binding = None
-        out = {
-            "metric": "Msamples/sec at 1920x1080, max-depth 8; MSE vs reference",
-            "value": round(value, 3),
-            "unit": "Msamples/sec",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 2),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": f"synthetic (procedural {args.scene} scene; the reference's glTF assets are not in its repo)",
-            "config": {
-                "workload": args.workload + (f", {world}xMI355X" if args.scaling == "strong" or world == 1
-                                             else f" per GPU, spp-sharded over {world} GPUs + RCCL reduce"),
-                "scene": args.scene,
-                "triangles": scene.n_triangles,
-                "width": args.width,
-                "height": args.height,
-                "spp_per_step": args.spp,
-                "spp_per_gpu_per_step": args.spp if args.scaling == "weak" else round(args.spp / world, 2),
-                "max_depth": args.depth,
-                "material_mode": {0: "default", 1: "lambert", 2: "conductor", 3: "dielectric",
-                                  4: "layered"}.get(scene.material_mode, str(scene.material_mode)),
-                "kernel": {0: "megakernel", 1: "wavefront", 2: "auto (wavefront)"}[args.kernel],
-                "frames_per_launch": args.frames_per_launch,
-                "wavefront_streams": eff_streams,
-                "parallelism": f"spp-shard x{world}",
-                "scene_source": source,
-                # the batches the timed region ran (pt_stats): frames per batch after the queue
-                # budget (pt_set_queue_budget, default a quarter of the device memory) and the
-                # device memory the wavefront queues held
-                "batch_frames": st["last_batch_frames"],
-                "queue_bytes": st["queue_bytes"],
-                "queue_budget_bytes": st["queue_budget"],
-                "bvh_build_ms": round(bvh_ms, 3),  # the first build in the process (code loading included)
-                # pt_options.bvh_builder = PT_BVH_AUTO: the binned-SAH binary tree built on the GPU
-                # (pt_sah_gpu.hip) and collapsed to BVH4 on the GPU; the time above covers both
-                "bvh_builder": "auto (GPU binned SAH + GPU SAH-optimal BVH4 collapse)",
-                "primary_dedup": args.kernel != 0,
-            },
+        out.update({
             # one extra step with pt_set_primary_dedup(0): each frame traces its own copy of the
             # (identical, unjittered) camera rays; same image bit for bit
             "value_primary_per_frame": None if value_nodedup is None else round(value_nodedup, 3),
@@ -623,11 +651,7 @@ def main():
                 "sources_sha": sha,
                 "pmc_stale": pmc_stale or None,
             },
-            "image": {"mean": float(np.nanmean(img) / per_step_spp), "nan_pixels": nan_px},
-            # what the process group ran: backend ("nccl" = RCCL), ranks, reduce time per step
-            "distributed": distributed,
-            "device": device_identity(torch, local_rank),
-        }
+        })
         if world == 1 and args.reference_loops > 0 and args.kernel != 0:
             # The reference's own call pattern (OptixView::DrawOptix -> OptixRenderer::Render,
             # OptixView.cpp:201-210, OptixRenderer.cpp:617-647): one pt_render per spp (frame.id++,
@@ -722,6 +746,7 @@ def main():
                 "gpu_frames_per_batch": fpl_check,
                 "gpu_streams": min(n_batches, eff_streams),
             }
+    if rank == 0:
         print(json.dumps(out), flush=True)
     r.close()
     if dist is not None:

@@ -20,7 +20,7 @@ if [ "$PART" = bench ]; then
   tail -1 "$OUT/gputest.log"
   for c in 2 3 4l 5 5t 4d; do
     echo "[round] bench config $c"
-    timeout -k 10 300 python3 bench.py --config $c > "$OUT/bench_config$c.json" 2> "$OUT/bench_config$c.log"
+    timeout -k 10 300 python3 bench.py --full --config $c > "$OUT/bench_config$c.json" 2> "$OUT/bench_config$c.log"
     cat "$OUT/bench_config$c.json"
   done
 else
