@@ -187,6 +187,15 @@ typedef struct pt_stats {
     int32_t last_streams;
     int32_t last_batch_frames;
     uint64_t look_ahead_held;
+    /* lit table (pt_set_lit_table): NEE visibility answers the shading kernels took from the table
+       instead of tracing a shadow ray (shadow_rays, pair_kernel_shadow_rays and nee_unoccluded keep
+       counting traced rays only); the table's cells per light, set bits over all lights, device
+       bytes, and the device time of its last build (0 while no table is in use) */
+    uint64_t lit_table_answers;
+    uint64_t lit_table_cells;
+    uint64_t lit_table_bits_set;
+    uint64_t lit_table_bytes;
+    double lit_table_build_ms;
 } pt_stats;
 
 typedef struct pt_renderer pt_renderer;
@@ -259,6 +268,33 @@ int pt_set_wavefront_streams(pt_renderer* r, int32_t streams);
  * render on two streams at once, each band's kernels filling the other's SIMT tails (default 1).
  * Every pixel's path depends only on its pixel and frame id: the image is bit-identical to 0. */
 int pt_set_band_split(pt_renderer* r, int32_t enable);
+/* Wavefront: the lit table, one bit per (point light, surface cell) that is set only where every
+ * NEE shadow ray from that cell toward that light is provably unoccluded (from the geometry and
+ * the light positions alone, any camera, any bounce).  The shading kernels add such a light's
+ * contribution at once instead of queueing a shadow ray; the images are bit-identical.  enable:
+ * < 0 auto (the default: on in the Lambert, Default and Layered modes, where it measured faster;
+ * off in Dielectric, which lost 1.2 %, in Conductor, not measured, and for pt_launch calls, whose
+ * one frame cannot pay for a build), 0 off, > 0 on (also for pt_launch: rebuilt on every such
+ * call, about 2 ms on a 35k-triangle scene, and again for the renderer's own lights afterwards).
+ * The table is rebuilt on the library stream when the lights change (pt_set_lights); it is not
+ * used with more than 16 lights, more than 2^23 cells or vertex coordinates beyond 128 units, and
+ * a light beyond 128 units has no bits (its shadow rays are traced). */
+int pt_set_lit_table(pt_renderer* r, int32_t enable);
+/* Tests: the lit table for the current lights (built now if it is stale).  info is always written;
+ * tri_words (one 32-bit word per leaf-ordered triangle: subdivision level << 24 | first cell, level
+ * 255 = no cells) and bits (lights x words_per_light 32-bit words) are copied when not NULL and
+ * their byte sizes match.  active = 0: no table (switched off, or one of the limits above). */
+typedef struct pt_lit_table_info {
+    int32_t active;
+    int32_t lights;
+    uint32_t triangles;
+    uint32_t cells;
+    uint32_t words_per_light;
+    float delta;
+    float margin;
+} pt_lit_table_info;
+int pt_lit_table_download(pt_renderer* r, pt_lit_table_info* info, uint32_t* tri_words, int64_t tri_bytes,
+                          uint32_t* bits, int64_t bits_bytes);
 
 /* LaunchParams (Renderer/OptiX/LaunchParams.h:9-28) as a C struct: the state one optixLaunch
  * reads.  Same fields and meaning; device pointers where the reference holds device pointers

@@ -143,7 +143,17 @@ class pt_stats(C.Structure):
         ("last_streams", C.c_int32),
         ("last_batch_frames", C.c_int32),
         ("look_ahead_held", C.c_uint64),
+        ("lit_table_answers", C.c_uint64),
+        ("lit_table_cells", C.c_uint64),
+        ("lit_table_bits_set", C.c_uint64),
+        ("lit_table_bytes", C.c_uint64),
+        ("lit_table_build_ms", C.c_double),
     ]
+
+
+class pt_lit_table_info(C.Structure):
+    _fields_ = [("active", C.c_int32), ("lights", C.c_int32), ("triangles", C.c_uint32), ("cells", C.c_uint32),
+                ("words_per_light", C.c_uint32), ("delta", C.c_float), ("margin", C.c_float)]
 
 
 class _pt_launch_frame(C.Structure):
@@ -194,6 +204,9 @@ SIGNATURES = {
     "pt_set_primary_dedup": (C.c_int, [_R, C.c_int32]),
     "pt_set_band_split": (C.c_int, [_R, C.c_int32]),
     "pt_set_wavefront_streams": (C.c_int, [_R, C.c_int32]),
+    "pt_set_lit_table": (C.c_int, [_R, C.c_int32]),
+    "pt_lit_table_download": (C.c_int, [_R, C.POINTER(pt_lit_table_info), C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_int64]),
     "pt_render_accumulate": (C.c_int, [_R, C.c_uint32, C.c_uint32, _FP]),
     "pt_set_accum_device_buffer": (C.c_int, [_R, C.c_void_p]),
     "pt_accum_device_ptr": (C.c_void_p, [_R]),

@@ -17,6 +17,7 @@
 
 #include "../../include/ptamd.h"
 #include "pt_internal.h"
+#include "pt_lit.h"
 
 using namespace pt;
 
@@ -262,6 +263,24 @@ struct pt_renderer {
     int debug_pixel = -1;
     uint32_t debug_frame = 0;
     float* d_debug = nullptr;
+    // lit table (pt_lit.h): the per-triangle words are fixed at pt_create (d_lit_tri NULL: the scene
+    // runs without it), the bits follow the lights: lit_prepare rebuilds them on `stream` when
+    // lit_version (bumped by pt_set_lights, and by a pt_launch with the table forced on, whose device light array the
+    // host cannot compare) or the light array differ from what they were built for
+    int lit_mode = -1;  // pt_set_lit_table: < 0 auto, 0 off, > 0 on
+    uint32_t* d_lit_tri = nullptr;
+    uint32_t* d_lit_bits = nullptr;  // kLitMaxLights * lit_words
+    uint32_t lit_cells = 0, lit_words = 0;
+    float lit_margin = 0.0f;
+    uint32_t lit_version = 1, lit_built_version = 0;
+    const void* lit_built_lights = nullptr;
+    int lit_built_n = 0;
+    bool lit_active = false;  // this call's launches read the table (make_launch)
+    bool lit_launch_call = false;  // inside pt_launch: auto leaves the table alone (lit_wanted)
+    hipEvent_t lit_ev[2] = {nullptr, nullptr};  // around the last build
+    bool lit_ev_pending = false;
+    double lit_build_ms = 0.0;
+    int64_t lit_bits_set = -1;  // of the last build; -1 = not counted yet (pt_get_stats)
 
     DevScene scene() const {
         DevScene S;
@@ -336,7 +355,52 @@ DevLaunch make_launch(const pt_renderer* r, float* accum, uint32_t frame_base, u
     L.debug_pixel = r->d_debug ? r->debug_pixel : -1;
     L.debug_frame = r->debug_frame;
     L.debug = r->d_debug;
+    L.lit_tri = r->lit_active ? r->d_lit_tri : nullptr;
+    L.lit_bits = r->d_lit_bits;
+    L.lit_words = r->lit_words;
     return L;
+}
+
+// The lit table for this call's lights (pt_lit.h): decides whether the call's launches use it
+// (r->lit_active) and rebuilds the bits when they are stale.  The build runs on r->stream, which
+// every earlier batch has joined (launch_frames), so batches already enqueued keep the bits they
+// were enqueued with until they are done, and the batches enqueued next see the new ones.
+#ifndef PT_LIT_TABLE
+#define PT_LIT_TABLE 1  // auto (pt_set_lit_table < 0): 1 = on where it pays, 0 = off (A/B builds)
+#endif
+bool lit_wanted(const pt_renderer* r) {
+    // auto: on in the modes where three interleaved runs per side cleared three times the parent's
+    // spread at 1080p (Lambert +6.8 %, Default +1.9 %, Layered +1.6 %); Dielectric lost 1.2 % (its
+    // register-bound k_shade_fused spills more) and Conductor is not measured
+    const bool pays = r->material_mode == PT_MAT_LAMBERT || r->material_mode == PT_MAT_DEFAULT ||
+                      r->material_mode == PT_MAT_LAYERED;
+    // A pt_launch call carries its own device light array, whose contents the host cannot compare
+    // with the built ones, and renders one frame, which cannot pay for a build (2 ms on the sphere
+    // box, about a 1080p frame): auto neither uses nor rebuilds the table there, and the table of the
+    // renderer's own lights stays valid.  pt_set_lit_table(1) rebuilds it for every such call.
+    const bool on = r->lit_mode < 0 ? PT_LIT_TABLE != 0 && pays && !r->lit_launch_call : r->lit_mode > 0;
+    return on && r->d_lit_tri && r->d_lights && r->n_lights >= 1 && r->n_lights <= kLitMaxLights;
+}
+int lit_prepare(pt_renderer* r) {
+    r->lit_active = lit_wanted(r);
+    if (!r->lit_active) return PT_OK;
+    if (r->lit_built_version == r->lit_version && r->lit_built_lights == r->d_lights && r->lit_built_n == r->n_lights)
+        return PT_OK;
+    if (!r->lit_ev[0]) {
+        PT_HIP(hipEventCreate(&r->lit_ev[0]), "hipEventCreate");
+        PT_HIP(hipEventCreate(&r->lit_ev[1]), "hipEventCreate");
+    }
+    PT_HIP(hipEventRecord(r->lit_ev[0], r->stream), "hipEventRecord");
+    PT_HIP(lit_build(r->scene(), r->d_lit_tri, r->lit_cells, r->lit_words, r->d_lights, r->n_lights, r->d_lit_bits,
+                     r->lit_margin, r->stream),
+           "lit_build");
+    PT_HIP(hipEventRecord(r->lit_ev[1], r->stream), "hipEventRecord");
+    r->lit_ev_pending = true;
+    r->lit_bits_set = -1;
+    r->lit_built_version = r->lit_version;
+    r->lit_built_lights = r->d_lights;
+    r->lit_built_n = r->n_lights;
+    return PT_OK;
 }
 
 // Bytes the wavefront queues of all streams hold now.
@@ -380,6 +444,7 @@ int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, doub
     const uint32_t chunk = (uint32_t)std::max(1, r->frames_per_launch);
     r->pending = true;
     r->band0_rows = 0;  // set below when this call renders its frame in row bands
+    r->lit_active = false;  // the wavefront branch decides (lit_prepare)
     // AUTO = wavefront: it beats the megakernel in every material mode (1080p
     // depth 8, 16 frames per launch, Msamples/s wavefront / megakernel: Lambert 725 / 414,
     // Dielectric 1239 / 758, Default 255 / 104).
@@ -502,6 +567,7 @@ int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, doub
             }
         int dev_cus = 256;
         (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, r->device);
+        if ((rc = lit_prepare(r)) != PT_OK) return rc;  // before the fork: every stream sees the new bits
         hipEvent_t a = nullptr, b = nullptr;  // dual: one event pair around the whole call
         if (dual) {
             rc = next_event_pair(r, &a, &b);
@@ -1160,6 +1226,19 @@ int pt_create(const pt_scene* scene, const pt_options* options, pt_renderer** ou
         if (3 * bo.depth > kMinTraversalStack)
             return cleanup_fail(fail(PT_ERR_INVALID, "pt_create: BVH too deep for the traversal stack (depth " +
                                                          std::to_string(bo.depth) + ")"));
+        // lit table: the cells of every leaf-ordered triangle (the bits follow the lights, lit_prepare)
+        std::vector<float4> isect_host(3 * ntri);
+        PT_HIPC(hipMemcpy(isect_host.data(), r->d_isect, sizeof(float4) * 3 * ntri, hipMemcpyDeviceToHost),
+                "download isect");
+        std::vector<uint32_t> lit_words_host;
+        if (lit_subdivide(isect_host.data(), (int)ntri, lit_words_host, &r->lit_cells, &r->lit_margin)) {
+            r->lit_words = (r->lit_cells + 31) / 32;
+            PT_HIPC(hipMalloc(&r->d_lit_tri, sizeof(uint32_t) * ntri), "hipMalloc lit table");
+            PT_HIPC(hipMalloc(&r->d_lit_bits, sizeof(uint32_t) * (size_t)r->lit_words * kLitMaxLights),
+                    "hipMalloc lit table");
+            PT_HIPC(hipMemcpy(r->d_lit_tri, lit_words_host.data(), sizeof(uint32_t) * ntri, hipMemcpyHostToDevice),
+                    "upload lit table");
+        }
     }
     PT_HIPC(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
 #undef PT_HIPC
@@ -1216,6 +1295,10 @@ int pt_destroy(pt_renderer* r) {
     if (r->d_texels) (void)hipFree(r->d_texels);
     if (r->d_texinfo) (void)hipFree(r->d_texinfo);
     if (r->d_lights) (void)hipFree(r->d_lights);
+    if (r->d_lit_tri) (void)hipFree(r->d_lit_tri);
+    if (r->d_lit_bits) (void)hipFree(r->d_lit_bits);
+    for (hipEvent_t e : r->lit_ev)
+        if (e) (void)hipEventDestroy(e);
     if (r->d_frame) (void)hipFree(r->d_frame);
     ring_free(r);
     if (r->d_accum) (void)hipFree(r->d_accum);
@@ -1330,7 +1413,8 @@ int pt_set_lights(pt_renderer* r, const pt_point_light* lights, int32_t count) {
     }
     r->n_lights = count;
     r->lights_version++;  // new contents, possibly in the same array: the render-ahead ring is stale
-    return PT_OK;
+    r->lit_version++;     // and so are the lit table's bits: rebuilt here, outside any timed render call
+    return lit_prepare(r);
 }
 
 int pt_set_max_bounces(pt_renderer* r, int32_t max_bounces) {
@@ -1417,6 +1501,8 @@ int pt_launch(pt_renderer* r, const pt_launch_params* lp) {
     r->d_lights = reinterpret_cast<DevLight*>(const_cast<pt_point_light*>(lp->point_lights));
     r->n_lights = lp->point_light_count;
     r->max_bounces = lp->max_bounces;
+    r->lit_launch_call = true;
+    if (r->lit_mode > 0) r->lit_version++;  // forced on: the array's contents may differ from call to call
     // colorBuffer[fbIndex] = pathRadiance (devicePrograms.cu:705): a one-frame sum into zeros
     hipError_t e = hipMemsetAsync(lp->frame.color_buffer, 0, sizeof(float) * 3 * (size_t)w * (size_t)h, r->stream);
     int rc = e == hipSuccess ? launch_frames(r, lp->frame.color_buffer, lp->frame.id, 1)
@@ -1429,6 +1515,7 @@ int pt_launch(pt_renderer* r, const pt_launch_params* lp) {
     r->d_lights = olights;
     r->n_lights = on;
     r->max_bounces = ob;
+    r->lit_launch_call = false;
     return rc;
 }
 
@@ -1656,6 +1743,32 @@ int pt_get_stats(pt_renderer* r, pt_stats* out) {
     out->last_streams = r->last_streams;
     out->last_batch_frames = r->last_batch;
     out->look_ahead_held = r->ahead_held;
+    out->lit_table_answers = c[27];
+    if (r->lit_ev_pending) {  // the last build's events (pt_synchronize above waited for them)
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, r->lit_ev[0], r->lit_ev[1]) == hipSuccess)
+            r->lit_build_ms = ms;
+        else
+            (void)hipGetLastError();
+        r->lit_ev_pending = false;
+    }
+    // the table's own figures only while it is in use: wanted for the renderer's state and built for its lights
+    if (lit_wanted(r) && r->lit_built_version == r->lit_version && r->lit_built_lights == r->d_lights &&
+        r->lit_built_n == r->n_lights) {
+        const size_t nw = (size_t)r->lit_words * (size_t)r->lit_built_n;
+        if (r->lit_bits_set < 0) {
+            std::vector<uint32_t> hb(nw);
+            PT_HIP(hipMemcpy(hb.data(), r->d_lit_bits, sizeof(uint32_t) * nw, hipMemcpyDeviceToHost),
+                   "download lit table");
+            int64_t n = 0;
+            for (uint32_t w : hb) n += __builtin_popcount(w);
+            r->lit_bits_set = n;
+        }
+        out->lit_table_cells = r->lit_cells;
+        out->lit_table_bits_set = (uint64_t)r->lit_bits_set;
+        out->lit_table_bytes = sizeof(uint32_t) * ((size_t)r->ntri + (size_t)r->lit_words * kLitMaxLights);
+        out->lit_table_build_ms = r->lit_build_ms;
+    }
     // a multi-device renderer reports the work of all its devices (times are device 0's)
     for (pt_renderer* p : r->peers) {
         pt_stats ps;
@@ -1683,6 +1796,7 @@ int pt_get_stats(pt_renderer* r, pt_stats* out) {
         out->pair_kernel_rays += ps.pair_kernel_rays;
         out->pair_kernel_bytes += ps.pair_kernel_bytes;
         out->pair_kernel_shadow_rays += ps.pair_kernel_shadow_rays;
+        out->lit_table_answers += ps.lit_table_answers;
         out->queue_bytes += ps.queue_bytes;
     }
     return PT_OK;
@@ -1977,6 +2091,43 @@ extern "C" int pt_set_primary_dedup(pt_renderer* r, int32_t enable) {
     r->primary_dedup = enable != 0;
     for (pt_renderer* p : r->peers) {
         if ((rc = pt_set_primary_dedup(p, enable)) != PT_OK) return rc;
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_set_lit_table(pt_renderer* r, int32_t enable) {
+    if (!r) return fail(PT_ERR_INVALID, "pt_set_lit_table: NULL");
+    const int mode = enable < 0 ? -1 : (enable > 0 ? 1 : 0);
+    r->lit_mode = mode;  // the images do not depend on it: frames rendered ahead stay valid
+    for (pt_renderer* p : r->peers) p->lit_mode = mode;
+    return PT_OK;
+}
+
+extern "C" int pt_lit_table_download(pt_renderer* r, pt_lit_table_info* info, uint32_t* tri_words, int64_t tri_bytes,
+                                     uint32_t* bits, int64_t bits_bytes) {
+    if (!r || !info) return fail(PT_ERR_INVALID, "pt_lit_table_download: NULL");
+    PT_HIP(hipSetDevice(r->device), "hipSetDevice");
+    int rc = lit_prepare(r);
+    if (rc) return rc;
+    std::memset(info, 0, sizeof *info);
+    info->active = r->lit_active ? 1 : 0;
+    info->delta = kLitDelta;
+    if (!r->lit_active) return PT_OK;
+    info->lights = r->n_lights;
+    info->triangles = (uint32_t)r->ntri;
+    info->cells = r->lit_cells;
+    info->words_per_light = r->lit_words;
+    info->margin = r->lit_margin;
+    PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
+    if (tri_words) {
+        if (tri_bytes != (int64_t)(sizeof(uint32_t) * (size_t)r->ntri))
+            return fail(PT_ERR_INVALID, "pt_lit_table_download: tri_words size mismatch");
+        PT_HIP(hipMemcpy(tri_words, r->d_lit_tri, (size_t)tri_bytes, hipMemcpyDeviceToHost), "download lit table");
+    }
+    if (bits) {
+        if (bits_bytes != (int64_t)(sizeof(uint32_t) * (size_t)r->lit_words * (size_t)r->n_lights))
+            return fail(PT_ERR_INVALID, "pt_lit_table_download: bits size mismatch");
+        PT_HIP(hipMemcpy(bits, r->d_lit_bits, (size_t)bits_bytes, hipMemcpyDeviceToHost), "download lit table");
     }
     return PT_OK;
 }

@@ -82,6 +82,11 @@ struct DevLaunch {
     int debug_pixel;
     uint32_t debug_frame;
     float* debug;
+    // lit table (pt_lit.h; wavefront shading kernels): per-triangle words, lit_words 32-bit words
+    // of bits per light; lit_tri NULL = no table, every shadow ray is traced
+    const uint32_t* lit_tri;
+    const uint32_t* lit_bits;
+    uint32_t lit_words;
 };
 constexpr int kDebugMaxBounces = 64;
 constexpr int kDebugRecordFloats = 22;  // ptamd.h pt_debug_bounce

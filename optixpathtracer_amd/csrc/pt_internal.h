@@ -118,6 +118,13 @@ hipError_t launch_render(int kernel, int mode, bool stats, const DevScene& S, co
 hipError_t launch_trace(const DevScene& S, const float* d_rays, int n, int* d_prim, float* d_thit, float* d_u,
                         float* d_v, int* d_back, int any_hit, hipStream_t stream);
 
+// Lit table (pt_lit.h, pt_lit.hip).  lit_subdivide: the per-triangle words from a host copy of the
+// leaf-ordered isect records; false = the scene runs without the table.  lit_build: clears and
+// rebuilds the bits of n_lights lights (`words` 32-bit words each) on `stream`.
+bool lit_subdivide(const float4* isect, int ntri, std::vector<uint32_t>& words, uint32_t* cells, float* margin);
+hipError_t lit_build(const DevScene& S, const uint32_t* tri_words, uint32_t cells, uint32_t words,
+                     const DevLight* lights, int n_lights, uint32_t* bits, float margin, hipStream_t stream);
+
 // Progressive view buffer (pt_display.hip).
 hipError_t display_fill(float* p, size_t n, float v, hipStream_t stream);
 hipError_t display_blend(float* fb, const float* frame, size_t n, float w, bool continuous, hipStream_t stream);

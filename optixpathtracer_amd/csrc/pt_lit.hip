@@ -1,0 +1,137 @@
+// pt_lit.hip — builds the lit table (pt_lit.h): the per-triangle subdivision on the host at
+// pt_create, the (light, cell) bits on the GPU whenever the lights change.
+#include "pt_internal.h"
+#include "pt_lit.h"
+
+namespace pt {
+
+// Per-triangle words from the leaf-ordered isect records (host copy).  False: the scene runs
+// without the table (no triangles, a coordinate beyond kLitMaxCoord or not finite, too many cells).
+bool lit_subdivide(const float4* isect, int ntri, std::vector<uint32_t>& words, uint32_t* cells, float* margin) {
+    words.clear();
+    *cells = 0;
+    *margin = 0.0f;
+    if (ntri <= 0) return false;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int t = 0; t < ntri; ++t) {
+        const float4 A = isect[3 * t], E1 = isect[3 * t + 1], E2 = isect[3 * t + 2];
+        const float v[3][3] = {{A.x, A.y, A.z}, {A.x + E1.x, A.y + E1.y, A.z + E1.z}, {A.x + E2.x, A.y + E2.y, A.z + E2.z}};
+        for (int k = 0; k < 3; ++k)
+            for (int a = 0; a < 3; ++a) {
+                if (!(fabsf(v[k][a]) <= kLitMaxCoord)) return false;  // also NaN
+                lo[a] = std::min(lo[a], v[k][a]);
+                hi[a] = std::max(hi[a], v[k][a]);
+            }
+    }
+    const double dx = (double)hi[0] - lo[0], dy = (double)hi[1] - lo[1], dz = (double)hi[2] - lo[2];
+    const float diag = (float)std::sqrt(dx * dx + dy * dy + dz * dz);
+    if (!(diag > 0.0f)) return false;
+    const float target = kLitCellFraction * diag;
+    words.resize((size_t)ntri);
+    uint64_t n = 0;
+    for (int t = 0; t < ntri; ++t) {
+        const float4 E1 = isect[3 * t + 1], E2 = isect[3 * t + 2];
+        const double a[3] = {E1.x, E1.y, E1.z}, b[3] = {E2.x, E2.y, E2.z}, o[3] = {0.0, 0.0, 0.0};
+        LitPlane p;
+        int k = kLitNoCells;
+        if (lit_plane_through(o, a, b, p)) {
+            const double l1 = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+            const double l2 = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+            const double c[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+            const double l3 = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+            k = lit_level_for((float)std::max(l1, std::max(l2, l3)), target);
+        }
+        if (n > kLitMaxCells) return false;
+        words[(size_t)t] = lit_word(k, (uint32_t)n);
+        n += lit_cells(k);
+    }
+    if (n == 0 || n > kLitMaxCells) return false;
+    *cells = (uint32_t)n;
+    *margin = lit_margin(diag);
+    return true;
+}
+
+namespace {
+
+// One wave per block with the walk stack in LDS (entry s of lane l at stk[s * 64 + l], conflict-free):
+// the kernel uses no scratch memory.  A private stack made it 400 B per lane, and the runtime's
+// scratch for the whole device (hundreds of MB, released again after the launch) moved the free
+// device memory under callers that size their allocations by it.
+constexpr int kLitBlock = 64;
+constexpr int kLitStack = 72;  // an unordered walk holds at most 3 entries per BVH4 level + 1 (pt_create: 3 * depth <= 71)
+
+__global__ __launch_bounds__(kLitBlock) void k_lit_build(DevScene S, const uint32_t* __restrict__ tri_words,
+                                                        uint32_t cells, uint32_t words, const DevLight* __restrict__ lights,
+                                                        int n_lights, uint32_t* __restrict__ bits, float margin) {
+    __shared__ int lds_stack[kLitStack * kLitBlock];
+    int* const stack = lds_stack + threadIdx.x;
+    const uint64_t id = (uint64_t)blockIdx.x * kLitBlock + threadIdx.x;
+    if (id >= (uint64_t)cells * (uint64_t)n_lights) return;
+    const int li = (int)(id / cells);
+    const uint32_t cell = (uint32_t)(id - (uint64_t)li * cells);
+    // the triangle of the cell: the last one whose first cell is <= cell (a triangle without
+    // cells shares its successor's first cell and sorts before it)
+    int a = 0, b = S.ntri - 1;
+    while (a < b) {
+        const int m = (a + b + 1) >> 1;
+        if (lit_first(tri_words[m]) <= cell) a = m; else b = m - 1;
+    }
+    const int t = a;
+    const uint32_t w = tri_words[t];
+    const int k = lit_level(w);
+    if (k == kLitNoCells || cell - lit_first(w) >= lit_cells(k)) return;
+    const float4 A = S.isect[3 * t], E1 = S.isect[3 * t + 1], E2 = S.isect[3 * t + 2];
+    const float v0[3] = {A.x, A.y, A.z}, e1[3] = {E1.x, E1.y, E1.z}, e2[3] = {E2.x, E2.y, E2.z};
+    const DevLight lt = lights[li];
+    const float lp[3] = {lt.px, lt.py, lt.pz};
+    // a light beyond the coordinate bound (or not finite) gets no bits: l - p would round by up to
+    // an ulp of l in the shading kernels' fp32 side test, no longer far below kLitDelta (pt_lit.h)
+    if (!(fabsf(lp[0]) <= kLitMaxCoord && fabsf(lp[1]) <= kLitMaxCoord && fabsf(lp[2]) <= kLitMaxCoord)) return;
+    LitPyramid P;
+    if (!lit_pyramid(v0, e1, e2, k, cell - lit_first(w), lp, kLitDelta, margin, P)) return;
+    int sp = 0;
+    stack[kLitBlock * sp++] = 0;  // the root is an inner node
+    while (sp > 0) {
+        const int c = stack[kLitBlock * --sp];
+        if (c >= 0) {
+            const BNode4 nd = S.nodes[c];
+            const float lox[4] = {nd.lox.x, nd.lox.y, nd.lox.z, nd.lox.w}, hix[4] = {nd.hix.x, nd.hix.y, nd.hix.z, nd.hix.w};
+            const float loy[4] = {nd.loy.x, nd.loy.y, nd.loy.z, nd.loy.w}, hiy[4] = {nd.hiy.x, nd.hiy.y, nd.hiy.z, nd.hiy.w};
+            const float loz[4] = {nd.loz.x, nd.loz.y, nd.loz.z, nd.loz.w}, hiz[4] = {nd.hiz.x, nd.hiz.y, nd.hiz.z, nd.hiz.w};
+            const int ch[4] = {nd.child.x, nd.child.y, nd.child.z, nd.child.w};
+            for (int q = 0; q < 4; ++q) {
+                if (ch[q] == kEmptyChild) continue;
+                const double lo[3] = {lox[q], loy[q], loz[q]}, hi[3] = {hix[q], hiy[q], hiz[q]};
+                if (lit_box_outside(P, lo, hi)) continue;
+                if (sp >= kLitStack) return;  // full stack: the bit stays 0
+                stack[kLitBlock * sp++] = ch[q];
+            }
+        } else {
+            const int first = leaf_first(c), cnt = leaf_count(c);
+            for (int q = 0; q < cnt; ++q) {
+                const int u = first + q;
+                const float4 UA = S.isect[3 * u], U1 = S.isect[3 * u + 1], U2 = S.isect[3 * u + 2];
+                const double pa[3] = {UA.x, UA.y, UA.z};
+                const double pb[3] = {(double)UA.x + U1.x, (double)UA.y + U1.y, (double)UA.z + U1.z};
+                const double pc[3] = {(double)UA.x + U2.x, (double)UA.y + U2.y, (double)UA.z + U2.z};
+                if (!lit_tri_outside(P, pa, pb, pc)) return;  // a possible occluder (cut-outs count as opaque)
+            }
+        }
+    }
+    atomicOr(&bits[(size_t)li * words + (cell >> 5)], 1u << (cell & 31));
+}
+
+}  // namespace
+
+// Clears and rebuilds the bits of n_lights lights (words 32-bit words each) on `stream`.
+hipError_t lit_build(const DevScene& S, const uint32_t* tri_words, uint32_t cells, uint32_t words,
+                     const DevLight* lights, int n_lights, uint32_t* bits, float margin, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(bits, 0, sizeof(uint32_t) * (size_t)words * (size_t)n_lights, stream);
+    if (e != hipSuccess || n_lights <= 0) return e;
+    const uint64_t n = (uint64_t)cells * (uint64_t)n_lights;
+    hipLaunchKernelGGL(k_lit_build, dim3((unsigned)((n + kLitBlock - 1) / kLitBlock)), dim3(kLitBlock), 0, stream, S,
+                       tri_words, cells, words, lights, n_lights, bits, margin);
+    return hipGetLastError();
+}
+
+}  // namespace pt

@@ -33,6 +33,7 @@
 #include <unordered_map>
 
 #include "pt_internal.h"
+#include "pt_lit.h"
 
 namespace pt {
 
@@ -876,6 +877,31 @@ __device__ __forceinline__ bool continue_path(const SurfaceHit& sf, const BSampl
     return next_bounce < max_bounces && length(beta) > 0.00001f;
 }
 
+// Lit table (pt_lit.h): the hit's cell (-1: a triangle without cells) and the (light, cell) bit.
+// A set bit answers the NEE visibility test of a hit whose shadow origin is offset to the light's
+// side, dot(l - p, Ng) > kLitDelta: unoccluded, no shadow ray.
+__device__ __forceinline__ int lit_cell(const DevLaunch& L, const Hit& h) {
+    const uint32_t w = L.lit_tri[h.tri];
+    const int k = lit_level(w);
+    return k == kLitNoCells ? -1 : (int)(lit_first(w) + lit_cell_index(k, h.u, h.v));
+}
+__device__ __forceinline__ bool lit_bit(const DevLaunch& L, int li, int cell) {
+    return (L.lit_bits[(size_t)li * L.lit_words + ((uint32_t)cell >> 5)] >> (cell & 31)) & 1u;
+}
+// Adds the block's table answers to pt_stats.lit_table_answers: every wave leaves its count in
+// lds[wave] before one of the block's barriers (lit_count_wave), thread 0 adds them up after it.
+__device__ __forceinline__ void lit_count_wave(bool answered, int* lds) {
+    const unsigned long long m = __ballot(answered ? 1 : 0);
+    if (lane_id() == 0) lds[threadIdx.x >> 6] = __popcll(m);
+}
+template <int WAVES>
+__device__ __forceinline__ void lit_count_block(const DevLaunch& L, const int* lds) {
+    if (threadIdx.x != 0 || !L.counters) return;
+    int tot = 0;
+    for (int w = 0; w < WAVES; ++w) tot += lds[w];
+    if (tot > 0) atomicAdd(&L.counters[27], (unsigned long long)tot);
+}
+
 // Bounce-0 shadow dedup (with primary dedup): a pixel's first hit is the same in every frame
 // of the batch, so its shadow ray toward light li is too.  k_shadow0_setup builds one shadow
 // ray per (pixel, light) from the frame-0 hit, k_shadow_vis traces them into W.vis[light *
@@ -931,13 +957,15 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
     float4* no = W.ray_o[(b + 1) & 1];
     float4* nd = W.ray_d[(b + 1) & 1];
     __shared__ int lds_sh[kSortKeys * kWaves + kSortKeys + 1], lds_q[kSortKeys * kWaves + kSortKeys + 1];
+    __shared__ int lds_lit[kWaves];
+    const bool lit = !vis0 && L.lit_tri;  // the lit table answers this bounce's NEE tests where it can
     if (blockIdx.x == 0 && threadIdx.x == 0 && L.counters) atomicAdd(&L.counters[15], (unsigned long long)n);
     if ((int)(blockIdx.x * kBlock) >= n) return;  // block-uniform
     {
         const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
         // a cancelled wave takes no item but still joins the block's appends (block_append)
         const bool valid = i < n && !wf_cancelled(W);
-        bool emit_shadow = false, emit_next = false;
+        bool emit_shadow = false, emit_next = false, lit_answer = false;
         f3 so, sdir, contrib, o, d, beta;
         uint32_t seed = 0;
         float stmax = 0.0f;
@@ -955,6 +983,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
             path = __float_as_int(hv.x);
             const Hit h = decode_hit(hv);
             if (h.tri >= 0) {  // a miss ends the path (__miss__radiance :576-583)
+                const int lit_c = lit ? lit_cell(L, h) : -1;  // fetched beside the surface records
                 const float4 c = shade0 ? ldqs(rd + path % P1) : c_q;
                 d = mk(c.x, c.y, c.z);
                 SurfaceHit sf;
@@ -988,8 +1017,11 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
                         float d2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
                         f3 Li = mk(lt.cr, lt.cg, lt.cb) / d2;
                         contrib = ((beta * spectrum) * Li) / (P * 1.0f);
-                        if (vis0) {  // bounce 0: the (pixel, light) visibility is already known
-                            if (W.vis[vis0_index(L, path, li)]) {
+                        // the lit table: the same add k_trace_pair would make for the unoccluded ray, at
+                        // the same place in the path's bounce order
+                        lit_answer = lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta && lit_bit(L, li, lit_c);
+                        if (vis0 || lit_answer) {  // the visibility is already known (bounce 0: per pixel and light)
+                            if (lit_answer || W.vis[vis0_index(L, path, li)]) {
                                 const float4 l = shade0 ? l0 : W.L[path];
                                 l0 = make_float4(l.x + contrib.x, l.y + contrib.y, l.z + contrib.z, 0.0f);
                                 if (!shade0) W.L[path] = l0;
@@ -1013,8 +1045,10 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
             }
         }
         if (shade0 && valid) W.L[path] = l0;  // every path of the batch, hit or miss
+        if (lit) lit_count_wave(lit_answer, lds_lit);
         const int qi = PT_SORT_EXT ? block_append_sorted<kWaves, kSortKeys>(cnt(W, b + 1, kQueue), emit_next ? octant(d) : -1, lds_q)
                                    : block_append<kWaves>(cnt(W, b + 1, kQueue), emit_next, lds_q);
+        if (lit) lit_count_block<kWaves>(L, lds_lit);
         if (emit_next) {
             stqs(no + qi, make_float4(o.x, o.y, o.z, __int_as_float(path)));
             stqs(nd + qi, make_float4(d.x, d.y, d.z, 0.0f));
@@ -1236,9 +1270,11 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
     const float4* rd = W.ray_d[b & 1];
     __shared__ int lds_sh[kWavesShA + 1];
     __shared__ int lds_nee[kNeeBuckets * (kWavesShA + 1)], lds_smp[kSmpBuckets * (kWavesShA + 1)];
+    __shared__ int lds_lit[kWavesShA];
+    const bool lit = !vis0 && L.lit_tri;  // as k_shade_fused
     if ((int)(blockIdx.x * kBlockShA) >= n) return;  // block-uniform
     const int i = (int)(blockIdx.x * kBlockShA + threadIdx.x);
-    bool emit = false;
+    bool emit = false, lit_answer = false;
     int nee_bucket = -1, smp_bucket = -1, code = 0;
     f3 so, sdir;
     float stmax = 0.0f;
@@ -1248,6 +1284,7 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
         const int path = __float_as_int(hv.x);
         const Hit h = decode_hit(hv);
         if (h.tri >= 0) {
+            const int lit_c = lit ? lit_cell(L, h) : -1;
             SurfaceHit sf;
             reconstruct<TEX>(S, h, mk(c.x, c.y, c.z), sf);
             float4 bv = W.beta[path];
@@ -1278,8 +1315,10 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
                 if (MODE == kModeLayered || !conductor)
                     nb = PT_NEE_CROSS && !same_hemisphere(sf.wo, to_local(sf.fr, ln)) ? kNeeCross
                                                                                      : nee_layered_bucket(bk, sf.albedo);
-                if (vis0) {
-                    if (W.vis[vis0_index(L, path, li)]) nee_bucket = nb;
+                // the lit table: known unoccluded, straight to the NEE queue like the bounce-0 table
+                lit_answer = lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta && lit_bit(L, li, lit_c);
+                if (vis0 || lit_answer) {
+                    if (lit_answer || W.vis[vis0_index(L, path, li)]) nee_bucket = nb;
                 } else {
                     so = sf.pos + 1e-3f * sf.ng;
                     sdir = ln;
@@ -1290,7 +1329,9 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
             }
         }
     }
+    if (lit) lit_count_wave(lit_answer, lds_lit);
     const int si = block_append<kWavesShA>(cnt(W, b, kShadowQ), emit, lds_sh);
+    if (lit) lit_count_block<kWavesShA>(L, lds_lit);
     if (emit) {
         W.sh_o[si] = make_float4(so.x, so.y, so.z, __int_as_float(code));
         W.sh_d[si] = make_float4(sdir.x, sdir.y, sdir.z, stmax);

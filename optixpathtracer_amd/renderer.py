@@ -235,6 +235,25 @@ class OptixRenderer:
         """One-frame calls: two row bands on two wavefront streams (pt_set_band_split, default on)."""
         check(self.lib.pt_set_band_split(self.h, 1 if enable else 0), "pt_set_band_split")
 
+    def set_lit_table(self, enable: bool | None) -> None:
+        """pt_set_lit_table: NEE answers from the (light, cell) lit table instead of shadow rays where
+        the table proves the light unoccluded; None = auto (the default), images bit-identical."""
+        check(self.lib.pt_set_lit_table(self.h, -1 if enable is None else (1 if enable else 0)), "pt_set_lit_table")
+
+    def lit_table(self):
+        """(info dict, tri_words (triangles,) uint32, bits (lights, words_per_light) uint32) of the lit
+        table for the current lights (pt_lit_table_download); (info, None, None) while it is off."""
+        info = capi.pt_lit_table_info()
+        check(self.lib.pt_lit_table_download(self.h, C.byref(info), None, 0, None, 0), "pt_lit_table_download")
+        d = {k: getattr(info, k) for k, _ in capi.pt_lit_table_info._fields_}
+        if not info.active:
+            return d, None, None
+        tri = np.zeros(info.triangles, np.uint32)
+        bits = np.zeros((info.lights, info.words_per_light), np.uint32)
+        check(self.lib.pt_lit_table_download(self.h, C.byref(info), tri.ctypes.data, tri.nbytes, bits.ctypes.data,
+                                             bits.nbytes), "pt_lit_table_download")
+        return d, tri, bits
+
     def render_accumulate(self, spp: int, first_frame_id: int = 1) -> np.ndarray:
         """Clear, render frame ids first_frame_id .. +spp-1 and return the mean image
         (pt_render_accumulate); the sum stays in the device accumulator."""
