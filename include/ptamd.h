@@ -291,7 +291,7 @@ typedef struct pt_lit_table_info {
     uint32_t cells;
     uint32_t words_per_light;
     float delta;
-    float margin;
+    float margin; /* the largest margin a cell can have; each (light, cell) uses its own, smaller one */
 } pt_lit_table_info;
 int pt_lit_table_download(pt_renderer* r, pt_lit_table_info* info, uint32_t* tri_words, int64_t tri_bytes,
                           uint32_t* bits, int64_t bits_bytes);

@@ -271,7 +271,7 @@ struct pt_renderer {
     uint32_t* d_lit_tri = nullptr;
     uint32_t* d_lit_bits = nullptr;  // kLitMaxLights * lit_words
     uint32_t lit_cells = 0, lit_words = 0;
-    float lit_margin = 0.0f;
+    float lit_diag = 0.0f;  // the scene box's diagonal: every cell's margin follows from it (lit_margin_cell)
     uint32_t lit_version = 1, lit_built_version = 0;
     const void* lit_built_lights = nullptr;
     int lit_built_n = 0;
@@ -392,7 +392,7 @@ int lit_prepare(pt_renderer* r) {
     }
     PT_HIP(hipEventRecord(r->lit_ev[0], r->stream), "hipEventRecord");
     PT_HIP(lit_build(r->scene(), r->d_lit_tri, r->lit_cells, r->lit_words, r->d_lights, r->n_lights, r->d_lit_bits,
-                     r->lit_margin, r->stream),
+                     r->lit_diag, r->stream),
            "lit_build");
     PT_HIP(hipEventRecord(r->lit_ev[1], r->stream), "hipEventRecord");
     r->lit_ev_pending = true;
@@ -1231,7 +1231,7 @@ int pt_create(const pt_scene* scene, const pt_options* options, pt_renderer** ou
         PT_HIPC(hipMemcpy(isect_host.data(), r->d_isect, sizeof(float4) * 3 * ntri, hipMemcpyDeviceToHost),
                 "download isect");
         std::vector<uint32_t> lit_words_host;
-        if (lit_subdivide(isect_host.data(), (int)ntri, lit_words_host, &r->lit_cells, &r->lit_margin)) {
+        if (lit_subdivide(isect_host.data(), (int)ntri, lit_words_host, &r->lit_cells, &r->lit_diag)) {
             r->lit_words = (r->lit_cells + 31) / 32;
             PT_HIPC(hipMalloc(&r->d_lit_tri, sizeof(uint32_t) * ntri), "hipMalloc lit table");
             PT_HIPC(hipMalloc(&r->d_lit_bits, sizeof(uint32_t) * (size_t)r->lit_words * kLitMaxLights),
@@ -2117,7 +2117,7 @@ extern "C" int pt_lit_table_download(pt_renderer* r, pt_lit_table_info* info, ui
     info->triangles = (uint32_t)r->ntri;
     info->cells = r->lit_cells;
     info->words_per_light = r->lit_words;
-    info->margin = r->lit_margin;
+    info->margin = lit_margin(r->lit_diag);  // the upper bound of the cells' margins (lit_margin_cell)
     PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
     if (tri_words) {
         if (tri_bytes != (int64_t)(sizeof(uint32_t) * (size_t)r->ntri))

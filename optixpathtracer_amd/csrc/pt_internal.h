@@ -120,10 +120,11 @@ hipError_t launch_trace(const DevScene& S, const float* d_rays, int n, int* d_pr
 
 // Lit table (pt_lit.h, pt_lit.hip).  lit_subdivide: the per-triangle words from a host copy of the
 // leaf-ordered isect records; false = the scene runs without the table.  lit_build: clears and
-// rebuilds the bits of n_lights lights (`words` 32-bit words each) on `stream`.
-bool lit_subdivide(const float4* isect, int ntri, std::vector<uint32_t>& words, uint32_t* cells, float* margin);
+// rebuilds the bits of n_lights lights (`words` 32-bit words each) on `stream`.  diagonal / diag: the
+// scene box's diagonal, from which every cell takes its margin (lit_margin_cell).
+bool lit_subdivide(const float4* isect, int ntri, std::vector<uint32_t>& words, uint32_t* cells, float* diagonal);
 hipError_t lit_build(const DevScene& S, const uint32_t* tri_words, uint32_t cells, uint32_t words,
-                     const DevLight* lights, int n_lights, uint32_t* bits, float margin, hipStream_t stream);
+                     const DevLight* lights, int n_lights, uint32_t* bits, float diag, hipStream_t stream);
 
 // Progressive view buffer (pt_display.hip).
 hipError_t display_fill(float* p, size_t n, float v, hipStream_t stream);

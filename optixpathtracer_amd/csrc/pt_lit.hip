@@ -7,10 +7,10 @@ namespace pt {
 
 // Per-triangle words from the leaf-ordered isect records (host copy).  False: the scene runs
 // without the table (no triangles, a coordinate beyond kLitMaxCoord or not finite, too many cells).
-bool lit_subdivide(const float4* isect, int ntri, std::vector<uint32_t>& words, uint32_t* cells, float* margin) {
+bool lit_subdivide(const float4* isect, int ntri, std::vector<uint32_t>& words, uint32_t* cells, float* diagonal) {
     words.clear();
     *cells = 0;
-    *margin = 0.0f;
+    *diagonal = 0.0f;
     if (ntri <= 0) return false;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int t = 0; t < ntri; ++t) {
@@ -47,7 +47,7 @@ bool lit_subdivide(const float4* isect, int ntri, std::vector<uint32_t>& words, 
     }
     if (n == 0 || n > kLitMaxCells) return false;
     *cells = (uint32_t)n;
-    *margin = lit_margin(diag);
+    *diagonal = diag;
     return true;
 }
 
@@ -62,7 +62,7 @@ constexpr int kLitStack = 72;  // an unordered walk holds at most 3 entries per 
 
 __global__ __launch_bounds__(kLitBlock) void k_lit_build(DevScene S, const uint32_t* __restrict__ tri_words,
                                                         uint32_t cells, uint32_t words, const DevLight* __restrict__ lights,
-                                                        int n_lights, uint32_t* __restrict__ bits, float margin) {
+                                                        int n_lights, uint32_t* __restrict__ bits, float diag) {
     __shared__ int lds_stack[kLitStack * kLitBlock];
     int* const stack = lds_stack + threadIdx.x;
     const uint64_t id = (uint64_t)blockIdx.x * kLitBlock + threadIdx.x;
@@ -88,6 +88,7 @@ __global__ __launch_bounds__(kLitBlock) void k_lit_build(DevScene S, const uint3
     // an ulp of l in the shading kernels' fp32 side test, no longer far below kLitDelta (pt_lit.h)
     if (!(fabsf(lp[0]) <= kLitMaxCoord && fabsf(lp[1]) <= kLitMaxCoord && fabsf(lp[2]) <= kLitMaxCoord)) return;
     LitPyramid P;
+    const float margin = lit_margin_cell(diag, lit_cell_reach(v0, e1, e2, k, cell - lit_first(w), lp));
     if (!lit_pyramid(v0, e1, e2, k, cell - lit_first(w), lp, kLitDelta, margin, P)) return;
     int sp = 0;
     stack[kLitBlock * sp++] = 0;  // the root is an inner node
@@ -123,14 +124,15 @@ __global__ __launch_bounds__(kLitBlock) void k_lit_build(DevScene S, const uint3
 
 }  // namespace
 
-// Clears and rebuilds the bits of n_lights lights (words 32-bit words each) on `stream`.
+// Clears and rebuilds the bits of n_lights lights (words 32-bit words each) on `stream`; diag: the
+// scene box's diagonal (lit_margin_cell).
 hipError_t lit_build(const DevScene& S, const uint32_t* tri_words, uint32_t cells, uint32_t words,
-                     const DevLight* lights, int n_lights, uint32_t* bits, float margin, hipStream_t stream) {
+                     const DevLight* lights, int n_lights, uint32_t* bits, float diag, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(bits, 0, sizeof(uint32_t) * (size_t)words * (size_t)n_lights, stream);
     if (e != hipSuccess || n_lights <= 0) return e;
     const uint64_t n = (uint64_t)cells * (uint64_t)n_lights;
     hipLaunchKernelGGL(k_lit_build, dim3((unsigned)((n + kLitBlock - 1) / kLitBlock)), dim3(kLitBlock), 0, stream, S,
-                       tri_words, cells, words, lights, n_lights, bits, margin);
+                       tri_words, cells, words, lights, n_lights, bits, diag);
     return hipGetLastError();
 }
 
