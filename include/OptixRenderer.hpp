@@ -155,6 +155,27 @@ class OptixRendererT {
         check(pt_render_accumulate(r_, spp, first_frame_id, reinterpret_cast<float*>(h_pixels)),
               "pt_render_accumulate");
     }
+    // --- beyond the reference: geometry updates on the live renderer (pt_commit_geometry).  The
+    // two setters stage a change; nothing renders differently until CommitGeometry.
+    template <class Mat4>
+    void SetMeshTransform(int mesh, const Mat4& modelMatrix) {  // column-major glm::mat4
+        float m[16];
+        for (int c = 0; c < 4; ++c)
+            for (int r = 0; r < 4; ++r) m[c * 4 + r] = modelMatrix[c][r];
+        check(pt_set_mesh_transform(r_, (int32_t)mesh, m), "pt_set_mesh_transform");
+    }
+    // New object-space vertices and normals of one mesh (the counts given at construction); an
+    // empty `normal` keeps the current normals.
+    template <class Vec3>
+    void UpdateMeshVertices(int mesh, const std::vector<Vec3>& vertecies, const std::vector<Vec3>& normal) {
+        static_assert(sizeof(Vec3) == 3 * sizeof(float), "vertices must be glm::vec3-like");
+        check(pt_set_mesh_vertices(r_, (int32_t)mesh, reinterpret_cast<const float*>(vertecies.data()),
+                                   normal.empty() ? nullptr : reinterpret_cast<const float*>(normal.data())),
+              "pt_set_mesh_vertices");
+    }
+    void CommitGeometry(bool rebuild = false) {
+        check(pt_commit_geometry(r_, rebuild ? PT_GEOM_REBUILD : PT_GEOM_REFIT), "pt_commit_geometry");
+    }
     pt_renderer* handle() { return r_; }
 
    private:

@@ -196,6 +196,22 @@ typedef struct pt_stats {
     uint64_t lit_table_bits_set;
     uint64_t lit_table_bytes;
     double lit_table_build_ms;
+    /* geometry updates (pt_commit_geometry): commits that changed something, how many of them ended on
+       a refitted and how many on a rebuilt tree, and the device time of the last commit's work (HIP
+       events around the re-bake, the level refits and the cost reduction, plus the build's own
+       device time for a rebuild) */
+    uint64_t geometry_commits;
+    uint64_t geometry_refits;
+    uint64_t geometry_rebuilds;
+    double geometry_commit_ms;
+    /* SAH cost of the BVH4 in force and of the tree as last built (pt_create or a rebuild): the
+       sum over nodes (the root included) and leaves of the stored box's half area times 1 per node
+       or 0.5 per leaf triangle (the collapse's constants), over the half area the root had when
+       the tree was last built.  Both use that one divisor, so their ratio is the ratio of the plain
+       area sums: a refit that stretches boxes raises it above 1 even when the scene box grows with
+       them.  fp64 in a fixed order: the same node array always gives the same number. */
+    double bvh_sah_cost;
+    double bvh_sah_cost_built;
 } pt_stats;
 
 typedef struct pt_renderer pt_renderer;
@@ -322,6 +338,33 @@ typedef struct pt_launch_params {
  * (the reference's CUDA_SYNC_CHECK).  The renderer's own size, camera, lights and max bounces are
  * not changed.  A zero size is a no-op; a negative max_bounces or count is PT_ERR_INVALID. */
 int pt_launch(pt_renderer* r, const pt_launch_params* params);
+
+/* ---- geometry updates on a live renderer -----------------------------------------------------
+ * The reference bakes its scene once (BuildAccel, OptixRenderer.cpp:306-456); these calls move a
+ * mesh without pt_destroy / pt_create: textures, queues, rings and every setting stay.  The two
+ * setters only STAGE a change: rendering is not affected until pt_commit_geometry.  Topology,
+ * texcoords and materials do not change.
+ * Stage a new model matrix (column-major, as pt_mesh.model_matrix) for mesh `mesh`. */
+int pt_set_mesh_transform(pt_renderer* r, int32_t mesh, const float model_matrix[16]);
+/* Stage new object-space vertices (n_vertices*3, the count given at pt_create) and, if not NULL,
+ * normals (n_vertices*3; NULL keeps the current ones).  PT_ERR_INVALID if normals are passed for a
+ * mesh that was created without them. */
+int pt_set_mesh_vertices(pt_renderer* r, int32_t mesh, const float* vertices, const float* normals);
+#define PT_GEOM_REFIT 0   /* keep the tree's topology, recompute every node box */
+#define PT_GEOM_REBUILD 1 /* rebuild with the builder chosen at pt_create */
+/* Apply the staged changes on every device of the renderer.  Nothing staged: a no-op returning
+ * PT_OK.  The commit cancels a speculative look-ahead batch (as a camera move does), waits for the
+ * rendering already enqueued, re-bakes the changed meshes' triangle records on the device and
+ * recomputes every BVH4 node box (both in place, bit-identical to what pt_create stores for the
+ * moved scene and this topology); PT_GEOM_REBUILD then builds a new tree as pt_create would and
+ * swaps it in.  SYNCHRONOUS in this version: it returns once the new geometry is in force (the lit
+ * table's cells are re-cut on the host).  Images are bit-identical to a renderer created from the
+ * moved scene, for a refit of any quality; pt_stats.bvh_sah_cost / bvh_sah_cost_built tells when a
+ * rebuild pays.  No frame rendered ahead before the commit is served after it.  The lit table
+ * follows: a vertex beyond 128 units switches it off, a later commit back inside switches it on.
+ * A rebuild whose tree is too deep for the traversal stack returns PT_ERR_INVALID and leaves the
+ * refitted tree (valid, with the new geometry) in force. */
+int pt_commit_geometry(pt_renderer* r, int32_t how);
 
 /* OptixRenderer::Render(glm::vec3 h_pixels[]) — OptixRenderer.cpp:617-647: frame.id++,
  * one sample per pixel, synchronous, downloads W*H*3 floats to host_rgb.  No-op before

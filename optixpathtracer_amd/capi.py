@@ -16,6 +16,7 @@ LIB_PATH = _HERE / "libptamd.so"
 PT_MAT_DEFAULT, PT_MAT_LAMBERT, PT_MAT_CONDUCTOR, PT_MAT_DIELECTRIC, PT_MAT_LAYERED = range(5)
 PT_KERNEL_MEGA, PT_KERNEL_WAVEFRONT, PT_KERNEL_AUTO = 0, 1, 2
 PT_BVH_AUTO, PT_BVH_LBVH, PT_BVH_SAH, PT_BVH_PLOC, PT_BVH_SAH_GPU = 0, 1, 2, 3, 4
+PT_GEOM_REFIT, PT_GEOM_REBUILD = 0, 1
 PT_OK, PT_ERR_INVALID, PT_ERR_HIP, PT_ERR_STATE, PT_ERR_NOMEM = 0, -1, -2, -3, -4
 
 MATERIAL_MODES = {
@@ -148,6 +149,12 @@ class pt_stats(C.Structure):
         ("lit_table_bits_set", C.c_uint64),
         ("lit_table_bytes", C.c_uint64),
         ("lit_table_build_ms", C.c_double),
+        ("geometry_commits", C.c_uint64),
+        ("geometry_refits", C.c_uint64),
+        ("geometry_rebuilds", C.c_uint64),
+        ("geometry_commit_ms", C.c_double),
+        ("bvh_sah_cost", C.c_double),
+        ("bvh_sah_cost_built", C.c_double),
     ]
 
 
@@ -189,6 +196,9 @@ SIGNATURES = {
     "pt_set_max_bounces": (C.c_int, [_R, C.c_int32]),
     "pt_set_material_mode": (C.c_int, [_R, C.c_int32]),
     "pt_set_kernel": (C.c_int, [_R, C.c_int32]),
+    "pt_set_mesh_transform": (C.c_int, [_R, C.c_int32, _FP]),
+    "pt_set_mesh_vertices": (C.c_int, [_R, C.c_int32, _FP, _FP]),
+    "pt_commit_geometry": (C.c_int, [_R, C.c_int32]),
     "pt_set_frames_per_launch": (C.c_int, [_R, C.c_int32]),
     "pt_set_render_ahead": (C.c_int, [_R, C.c_int32]),
     "pt_set_render_ahead_budget": (C.c_int, [_R, C.c_float]),

@@ -215,18 +215,13 @@ __device__ __forceinline__ float half_area(float4 lo, float4 hi) {
 //   single(n)  = min(A(n) * cTri * count(n)            [leaf, count <= kSahLeafMax],
 //                   A(n) * cNode + min_a cost[L][a] + cost[R][4 - a])   [BVH4 node]
 //   cost[n][1] = single(n);  cost[n][j] = min(single(n), min_a cost[L][a] + cost[R][j - a])
-// The top-down k_collapse_sah then replays the recorded choices.  With the dual traversal
-// step (pt_device.h) a triangle test overlaps a node visit, hence cTri < cNode.
+// The top-down k_collapse_sah then replays the recorded choices.  kSahCNode and kSahCTri:
+// pt_internal.h.
 #ifndef PT_SAH_LEAF_MAX
 #define PT_SAH_LEAF_MAX 4
 #endif
-#ifndef PT_SAH_CTRI
-#define PT_SAH_CTRI 0.5f
-#endif
 constexpr int kSahLeafMax = PT_SAH_LEAF_MAX;
 static_assert(kSahLeafMax >= 1 && kSahLeafMax <= 8, "leaf count is encoded in 3 bits");
-constexpr float kSahCNode = 1.0f;
-constexpr float kSahCTri = PT_SAH_CTRI;
 
 // Decision word of an internal node: bits 2(j-2)..2(j-2)+1 for j = 2..4 = left pieces a of the
 // best split into j (0 = keep single); bits 6..7 = left pieces of the node's own 4-way split;
@@ -665,6 +660,7 @@ hipError_t lbvh_build(const BuildInput& in, BuildOutput& out, hipStream_t stream
     if (ms) *ms = 0.0f;
     out.n_nodes = 0;
     out.depth = 0;
+    out.level_base.clear();
     if (n <= 0) return hipSuccess;
     while ((1 << levels) <= n) ++levels;  // levels 0..levels-1 with 2^l <= n
     PT_TRY(hipEventCreate(&e0));
@@ -801,6 +797,7 @@ hipError_t lbvh_build(const BuildInput& in, BuildOutput& out, hipStream_t stream
         // level 0: the binary root (or the single leaf ~0) -> BVH4 slot 0
         PT_TRY(hipMemcpyAsync(work, &root, sizeof(int), hipMemcpyHostToDevice, stream));
         while (nwork > 0) {
+            out.level_base.push_back(level_base);
             hipLaunchKernelGGL(k_collapse_count, dim3(grid_for(nwork, 128)), dim3(128), 0, stream, B, dp_dec, work,
                                nwork, wcnt);
             PT_TRY(hipGetLastError());
@@ -824,6 +821,7 @@ hipError_t lbvh_build(const BuildInput& in, BuildOutput& out, hipStream_t stream
     if (ms) PT_TRY(hipEventElapsedTime(ms, e0, e1));
     out.n_nodes = node_count;
     out.depth = depth;
+    out.level_base.push_back(node_count);
 done:
     (void)hipStreamSynchronize(stream);
     for (void* p : {(void*)keys, (void*)vals, (void*)keys2, (void*)vals2, (void*)st, (void*)bchild, (void*)brange,

@@ -98,6 +98,100 @@ constexpr size_t kMaxPendingEvents = 4096;
 // wavefront's 11 LDS entries and 64 spill slots in chunks of 5)
 constexpr int kMinTraversalStack = std::min(stack_capacity(PT_WF_STACK), stack_capacity(PT_MK_STACK));
 
+// The scene as pt_create received it, kept for geometry updates (pt_commit_geometry): object-space
+// vertices and normals of all meshes concatenated, per-triangle global vertex indices in original
+// order, the per-mesh matrices, and what else the bake and a rebuild need.
+struct GeomHost {
+    std::vector<float4> verts, norms;  // xyz | 0; norms are zeros for a mesh without normals
+    std::vector<int4> tidx;            // per original triangle: three indices into verts, w = mesh
+    std::vector<float> model;          // 16 per mesh
+    std::vector<int> voff;             // first vertex of mesh m (n_meshes + 1 entries)
+    std::vector<int> has_normals, alpha;  // per mesh: normals given; albedo-textured (cut-out flag)
+    std::vector<float4> uvs;           // 2 per triangle, textured scenes only
+    int n_meshes() const { return (int)has_normals.size(); }
+    // pt_device.h normal mode of mesh m under its present matrix: kNormalBaked where the 3x3 part has
+    // at most one entry per row and that entry is +-1 (transforming the vertex normals first then
+    // gives the bits of the reference's order), kNormalObject otherwise
+    int normal_mode(int m) const {
+        if (!has_normals[(size_t)m]) return 0;
+        const float* M = &model[16 * (size_t)m];
+        for (int r = 0; r < 3; ++r) {
+            int nonzero = 0;
+            for (int c = 0; c < 3; ++c) {
+                const float e = M[4 * c + r];
+                if (e != 0.0f) ++nonzero;
+                if (e != 0.0f && e != 1.0f && e != -1.0f) return 2;
+            }
+            if (nonzero > 1) return 2;
+        }
+        return 1;
+    }
+    // rows [1].y and [3..5] of mesh m's material record (pt_device.h): the normal mode and the matrix rows
+    void normal_rows(int m, float4* rec) const {
+        const float* M = &model[16 * (size_t)m];
+        rec[1].y = (float)normal_mode(m);
+        for (int r = 0; r < 3; ++r) rec[3 + r] = make_float4(M[r], M[4 + r], M[8 + r], M[12 + r]);
+    }
+};
+
+// The bake: world-space triangle soup in original order (modelMatrix * vec4(v, 1); normals with
+// w = 0) with its w tags, and the centroid bounds.  pt_create and the rebuild path of
+// pt_commit_geometry both call it; k_rebake (pt_refit.hip) runs the same arithmetic per triangle.
+void bake_scene(const GeomHost& G, std::vector<float4>& tri, std::vector<float4>& nrm, float cmin[3], float cmax[3]) {
+    const size_t ntri = G.tidx.size(), nv = G.verts.size();
+    tri.resize(3 * ntri);
+    nrm.resize(3 * ntri);
+    std::vector<float> wv(3 * nv), wn(3 * nv, 0.0f);
+    for (int m = 0; m < G.n_meshes(); ++m) {
+        const float* M = &G.model[16 * (size_t)m];
+        for (int v = G.voff[(size_t)m]; v < G.voff[(size_t)m + 1]; ++v) {
+            const float4 p = G.verts[(size_t)v];
+            float in4[4] = {p.x, p.y, p.z, 1.0f}, o4[4];
+            xform4(M, in4, o4);
+            wv[3 * (size_t)v] = o4[0];
+            wv[3 * (size_t)v + 1] = o4[1];
+            wv[3 * (size_t)v + 2] = o4[2];
+            const int mode = G.normal_mode(m);
+            if (mode != 0) {
+                const float4 q = G.norms[(size_t)v];
+                float n4[4] = {q.x, q.y, q.z, 0.0f};
+                o4[0] = q.x, o4[1] = q.y, o4[2] = q.z;  // kNormalObject: reconstruct applies the matrix
+                if (mode == 1) xform4(M, n4, o4);
+                wn[3 * (size_t)v] = o4[0];
+                wn[3 * (size_t)v + 1] = o4[1];
+                wn[3 * (size_t)v + 2] = o4[2];
+            }
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        cmin[a] = INFINITY;
+        cmax[a] = -INFINITY;
+    }
+    for (size_t t = 0; t < ntri; ++t) {
+        const int4 id = G.tidx[t];
+        const int vi3[3] = {id.x, id.y, id.z}, m = id.w;
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int k = 0; k < 3; ++k) {
+            const size_t vi = (size_t)vi3[k];
+            float wbits;
+            // w tags: v0 = original triangle index, v1 = mesh, v2 = alpha cut-out flag
+            int tag = (k == 0) ? (int)t : (k == 1 ? m : G.alpha[(size_t)m]);
+            std::memcpy(&wbits, &tag, 4);
+            tri[3 * t + k] = make_float4(wv[3 * vi], wv[3 * vi + 1], wv[3 * vi + 2], wbits);
+            nrm[3 * t + k] = make_float4(wn[3 * vi], wn[3 * vi + 1], wn[3 * vi + 2], 0.0f);
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = std::min(lo[a], wv[3 * vi + a]);
+                hi[a] = std::max(hi[a], wv[3 * vi + a]);
+            }
+        }
+        for (int a = 0; a < 3; ++a) {
+            float c = 0.5f * (lo[a] + hi[a]);
+            cmin[a] = std::min(cmin[a], c);
+            cmax[a] = std::max(cmax[a], c);
+        }
+    }
+}
+
 }  // namespace
 
 struct pt_renderer {
@@ -116,6 +210,31 @@ struct pt_renderer {
     float4* d_isect = nullptr;
     float4* d_shade = nullptr;
     int bvh_nodes = 0, bvh_depth = 0;
+    // geometry updates (pt_set_mesh_transform / pt_set_mesh_vertices / pt_commit_geometry): the
+    // retained scene on the host and on the device, the changes staged since the last commit, the
+    // tree's level bases for the refit, and the SAH cost of the tree now and as last built
+    GeomHost geom;
+    std::vector<float4> mats;  // host copy of d_mats: a new matrix rewrites its mesh's normal mode and rows
+    struct StagedMesh {
+        bool has_model = false, has_verts = false, has_norms = false;
+        float model[16];
+        std::vector<float> verts, norms;
+    };
+    std::vector<StagedMesh> staged;
+    bool geom_staged = false;
+    int builder = kBuilderSAHGPU;
+    std::vector<int> level_base;
+    float4* d_overts = nullptr;
+    float4* d_onorms = nullptr;
+    int4* d_tidx = nullptr;
+    RefitMesh* d_rmesh = nullptr;
+    double* d_sah_part = nullptr;  // sah_partial_blocks(max(1, ntri)) + 1 doubles
+    hipEvent_t geom_ev[2] = {nullptr, nullptr};
+    uint32_t geom_version = 0;  // bumped per commit: no ring frame rendered before it is served after
+    uint64_t geom_commits = 0, geom_refits = 0, geom_rebuilds = 0;
+    double geom_commit_ms = 0.0;
+    double sah_cost = 0.0, sah_cost_built = 0.0;
+    double sah_root_built = 0.0;  // the root's half area as last built: both costs are relative to it
     bool trav_stats = false;
     WFState wf;
     float4* d_mats = nullptr;
@@ -144,13 +263,14 @@ struct pt_renderer {
     // frame ids download them from the ring
     struct RenderKey {
         int w = 0, h = 0, n_lights = 0, max_bounces = 0, mode = 0, kernel = 0, debug_pixel = -1;
-        uint32_t lights_version = 0, debug_frame = 0, debug_version = 0;
+        uint32_t lights_version = 0, debug_frame = 0, debug_version = 0, geom_version = 0;
         const void* lights = nullptr;
         float cam[3 + 16 + 16] = {};
         bool operator==(const RenderKey& o) const {
             return w == o.w && h == o.h && n_lights == o.n_lights && max_bounces == o.max_bounces && mode == o.mode &&
                    kernel == o.kernel && debug_pixel == o.debug_pixel && lights_version == o.lights_version &&
-                   debug_frame == o.debug_frame && debug_version == o.debug_version && lights == o.lights &&
+                   debug_frame == o.debug_frame && debug_version == o.debug_version && geom_version == o.geom_version &&
+                   lights == o.lights &&
                    std::memcmp(cam, o.cam, sizeof cam) == 0;
         }
     };
@@ -271,6 +391,7 @@ struct pt_renderer {
     uint32_t* d_lit_tri = nullptr;
     uint32_t* d_lit_bits = nullptr;  // kLitMaxLights * lit_words
     uint32_t lit_cells = 0, lit_words = 0;
+    uint32_t lit_words_cap = 0;  // words per light d_lit_bits has room for (a commit may grow the table)
     float lit_diag = 0.0f;  // the scene box's diagonal: every cell's margin follows from it (lit_margin_cell)
     uint32_t lit_version = 1, lit_built_version = 0;
     const void* lit_built_lights = nullptr;
@@ -672,7 +793,7 @@ int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, doub
 
 bool valid_mode(int m) { return m >= PT_MAT_DEFAULT && m <= PT_MAT_LAYERED; }
 
-// Everything a 1-spp image depends on besides its frame id (the scene is fixed at pt_create).
+// Everything a 1-spp image depends on besides its frame id (the geometry by its commit count).
 pt_renderer::RenderKey render_key(const pt_renderer* r) {
     pt_renderer::RenderKey k;
     k.w = r->width;
@@ -685,6 +806,7 @@ pt_renderer::RenderKey render_key(const pt_renderer* r) {
     k.debug_frame = r->debug_frame;
     k.lights_version = r->lights_version;
     k.debug_version = r->debug_version;
+    k.geom_version = r->geom_version;
     k.lights = r->d_lights;
     std::memcpy(k.cam, r->cam_pos, sizeof r->cam_pos);
     std::memcpy(k.cam + 3, r->inv_view, sizeof r->inv_view);
@@ -997,6 +1119,126 @@ int alloc_accum64(pt_renderer* r, int width, int height) {
     return PT_OK;
 }
 
+// A mesh whose normals stay in object space (pt_device.h kNormalObject) needs the kernels'
+// TEX instantiations, which S.texinfo selects: an untextured scene gets a one-entry array that no
+// record refers to.
+int need_tex_kernels(pt_renderer* r) {
+    if (r->d_texinfo) return PT_OK;
+    bool any = false;
+    for (int m = 0; m < r->nmesh; ++m) any = any || r->geom.normal_mode(m) == 2;
+    if (!any) return PT_OK;
+    PT_HIP(hipMalloc(&r->d_texinfo, sizeof(int4)), "hipMalloc texinfo");
+    PT_HIP(hipMemset(r->d_texinfo, 0, sizeof(int4)), "hipMemset texinfo");
+    return PT_OK;
+}
+
+// Upload the baked soup and build the BVH4 and the leaf-ordered records into `bo`'s buffers with the
+// renderer's builder; *ms (optional) = device time of the build.  Synchronises the library stream.
+int build_tree(pt_renderer* r, const std::vector<float4>& tri, const std::vector<float4>& nrm, const float cmin[3],
+               const float cmax[3], BuildOutput& bo, float* ms_out = nullptr) {
+    const size_t ntri = tri.size() / 3;
+    float4 *d_tri_orig = nullptr, *d_nrm_orig = nullptr, *d_uv_orig = nullptr;
+    hipError_t e = hipMalloc(&d_tri_orig, sizeof(float4) * 3 * ntri);
+    if (e == hipSuccess) e = hipMalloc(&d_nrm_orig, sizeof(float4) * 3 * ntri);
+    if (e == hipSuccess && bo.tuv) e = hipMalloc(&d_uv_orig, sizeof(float4) * 2 * ntri);
+    if (e == hipSuccess && bo.tuv)
+        e = hipMemcpyAsync(d_uv_orig, r->geom.uvs.data(), sizeof(float4) * 2 * ntri, hipMemcpyHostToDevice, r->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_tri_orig, tri.data(), sizeof(float4) * 3 * ntri, hipMemcpyHostToDevice, r->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_nrm_orig, nrm.data(), sizeof(float4) * 3 * ntri, hipMemcpyHostToDevice, r->stream);
+    float ms = 0.0f;
+    if (e == hipSuccess) {
+        BuildInput in;
+        in.tri_orig = d_tri_orig;
+        in.nrm_orig = d_nrm_orig;
+        in.uv_orig = d_uv_orig;
+        in.n = (int)ntri;
+        // AUTO: the binned-SAH tree (fewest node visits of the builders, DESIGN.md §5), built on the
+        // GPU; every peer of a multi-device renderer builds its own on its own device
+        in.builder = r->builder;
+        in.tri_host = tri.data();
+        for (int a = 0; a < 3; ++a) {
+            in.cmin[a] = cmin[a];
+            in.cmax[a] = cmax[a];
+        }
+        e = lbvh_build(in, bo, r->stream, &ms);
+    }
+    (void)hipStreamSynchronize(r->stream);
+    if (d_tri_orig) (void)hipFree(d_tri_orig);
+    if (d_nrm_orig) (void)hipFree(d_nrm_orig);
+    if (d_uv_orig) (void)hipFree(d_uv_orig);
+    if (e != hipSuccess) return hip_fail(e, "lbvh_build");
+    if (ms_out) *ms_out = ms;
+    else r->bvh_ms = ms;
+    return PT_OK;
+}
+
+// The SAH cost of the BVH4 in force -> r->sah_cost (pt_stats bvh_sah_cost): the sum over every node
+// and leaf of its stored box's half area times kSahCNode (a node, the root included) or kSahCTri x
+// triangles (a leaf), in fp64 -- per-block partials (k_sah_partial) added here in block order --
+// over the half area the root had when the tree was last built.  `built`: the tree was just
+// built, so that root is this one and bvh_sah_cost_built takes the same value.  `after` (optional)
+// is recorded behind the kernel.  Synchronises the library stream.
+int sah_cost_now(pt_renderer* r, bool built, hipEvent_t after = nullptr) {
+    const int nb = sah_partial_blocks(r->bvh_nodes);
+    std::vector<double> part((size_t)nb + 1, 0.0);
+    if (nb > 0) PT_HIP(sah_partial_launch(r->d_nodes, r->bvh_nodes, r->d_sah_part, r->stream), "k_sah_partial");
+    if (after) PT_HIP(hipEventRecord(after, r->stream), "hipEventRecord");
+    if (nb > 0)
+        PT_HIP(hipMemcpyAsync(part.data(), r->d_sah_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, r->stream),
+               "download SAH partials");
+    PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
+    double sum = 0.0;
+    for (int b = 0; b < nb; ++b) sum += part[(size_t)b];
+    if (built) r->sah_root_built = part[(size_t)nb];
+    r->sah_cost = r->sah_root_built > 0.0 ? sum / r->sah_root_built : 0.0;
+    if (built) r->sah_cost_built = r->sah_cost;
+    return PT_OK;
+}
+
+// The lit table's cells for the leaf-ordered records in force (pt_create, and every geometry
+// commit): lit_subdivide on a host copy; a scene outside the table's limits runs without it until
+// a later commit brings it back inside.  The bits are stale either way (lit_version).
+int lit_resubdivide(pt_renderer* r) {
+    const size_t ntri = (size_t)r->ntri;
+    std::vector<float4> isect_host(3 * ntri);
+    PT_HIP(hipMemcpy(isect_host.data(), r->d_isect, sizeof(float4) * 3 * ntri, hipMemcpyDeviceToHost), "download isect");
+    std::vector<uint32_t> lit_words_host;
+    uint32_t cells = 0;
+    float diag = 0.0f;
+    r->lit_version++;
+    r->lit_bits_set = -1;
+    if (!lit_subdivide(isect_host.data(), (int)ntri, lit_words_host, &cells, &diag)) {
+        if (r->d_lit_tri) (void)hipFree(r->d_lit_tri);
+        r->d_lit_tri = nullptr;  // lit_wanted: no table
+        r->lit_cells = r->lit_words = 0;
+        return PT_OK;
+    }
+    const uint32_t words = (cells + 31) / 32;
+    hipError_t e = hipSuccess;
+    if (words > r->lit_words_cap) {
+        if (r->d_lit_bits) (void)hipFree(r->d_lit_bits);
+        r->d_lit_bits = nullptr;
+        r->lit_words_cap = 0;
+        e = hipMalloc(&r->d_lit_bits, sizeof(uint32_t) * (size_t)words * kLitMaxLights);
+        if (e == hipSuccess) r->lit_words_cap = words;
+    }
+    if (e == hipSuccess && !r->d_lit_tri) e = hipMalloc(&r->d_lit_tri, sizeof(uint32_t) * ntri);
+    if (e == hipSuccess)
+        e = hipMemcpy(r->d_lit_tri, lit_words_host.data(), sizeof(uint32_t) * ntri, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {  // no table rather than a stale one
+        if (r->d_lit_tri) (void)hipFree(r->d_lit_tri);
+        r->d_lit_tri = nullptr;
+        r->lit_cells = r->lit_words = 0;
+        return hip_fail(e, "lit table");
+    }
+    r->lit_cells = cells;
+    r->lit_words = words;
+    r->lit_diag = diag;
+    return PT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1063,10 +1305,11 @@ int pt_create(const pt_scene* scene, const pt_options* options, pt_renderer** ou
             any_tex = any_tex || id >= 0;
         }
     }
-    std::vector<float4> tri(3 * ntri), nrm(3 * ntri), uvs(any_tex ? 2 * ntri : 0);
     std::vector<float4> mats((size_t)kMatStride * (size_t)std::max(1, scene->n_meshes));
-    float cmin[3] = {INFINITY, INFINITY, INFINITY}, cmax[3] = {-INFINITY, -INFINITY, -INFINITY};
-    size_t t = 0;
+    GeomHost G;
+    G.voff.push_back(0);
+    G.tidx.reserve(ntri);
+    if (any_tex) G.uvs.reserve(2 * ntri);
     for (int m = 0; m < scene->n_meshes; ++m) {
         const pt_mesh& me = scene->meshes[m];
         auto ibits = [](int v) {
@@ -1077,27 +1320,25 @@ int pt_create(const pt_scene* scene, const pt_options* options, pt_renderer** ou
         const bool textured = me.albedo_tex >= 0 || me.normal_tex >= 0 || me.metal_rough_tex >= 0;
         mats[kMatStride * m] = make_float4(me.albedo[0], me.albedo[1], me.albedo[2], me.metallic);
         mats[kMatStride * m + 1] =
-            make_float4(me.roughness, me.normals ? 1.0f : 0.0f, ibits(me.albedo_tex), ibits(me.normal_tex));
+            make_float4(me.roughness, kNormalNone, ibits(me.albedo_tex), ibits(me.normal_tex));  // .y: normal_rows
         mats[kMatStride * m + 2] = make_float4(ibits(me.metal_rough_tex), textured ? 1.0f : 0.0f, 0.0f, 0.0f);
-        // world-space vertices (modelMatrix * vec4(v,1)); normals pre-transformed with w = 0
-        std::vector<float> wv(3 * (size_t)me.n_vertices), wn(3 * (size_t)me.n_vertices, 0.0f);
-        for (int v = 0; v < me.n_vertices; ++v) {
-            float in4[4] = {me.vertices[3 * v], me.vertices[3 * v + 1], me.vertices[3 * v + 2], 1.0f}, o4[4];
-            xform4(me.model_matrix, in4, o4);
-            wv[3 * v] = o4[0];
-            wv[3 * v + 1] = o4[1];
-            wv[3 * v + 2] = o4[2];
-            if (me.normals) {
-                float n4[4] = {me.normals[3 * v], me.normals[3 * v + 1], me.normals[3 * v + 2], 0.0f};
-                xform4(me.model_matrix, n4, o4);
-                wn[3 * v] = o4[0];
-                wn[3 * v + 1] = o4[1];
-                wn[3 * v + 2] = o4[2];
-            }
+        // retained: object-space vertices and normals, the matrix, global vertex indices
+        const int voff = G.voff.back(), nv = me.vertices ? me.n_vertices : 0;
+        if ((size_t)voff + (size_t)nv > (size_t)0x7fffffff) return fail(PT_ERR_INVALID, "pt_create: too many vertices");
+        for (int v = 0; v < nv; ++v) {
+            G.verts.push_back(make_float4(me.vertices[3 * v], me.vertices[3 * v + 1], me.vertices[3 * v + 2], 0.0f));
+            G.norms.push_back(me.normals
+                                  ? make_float4(me.normals[3 * v], me.normals[3 * v + 1], me.normals[3 * v + 2], 0.0f)
+                                  : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
         }
-        for (int i = 0; i < me.n_triangles; ++i, ++t) {
-            float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        G.voff.push_back(voff + nv);
+        G.has_normals.push_back(me.normals ? 1 : 0);
+        G.alpha.push_back(me.albedo_tex >= 0 ? 1 : 0);
+        G.model.insert(G.model.end(), me.model_matrix, me.model_matrix + 16);
+        G.normal_rows(m, &mats[(size_t)kMatStride * (size_t)m]);
+        for (int i = 0; i < me.n_triangles; ++i) {
             float uv[6] = {0, 0, 0, 0, 0, 0};  // Mesh::texCoord, zeros when absent (Mesh.cpp:50-53)
+            int gi[3];
             for (int k = 0; k < 3; ++k) {
                 int vi = me.indices[3 * i + k];
                 if (vi < 0 || vi >= me.n_vertices) return fail(PT_ERR_INVALID, "pt_create: index out of range");
@@ -1105,28 +1346,18 @@ int pt_create(const pt_scene* scene, const pt_options* options, pt_renderer** ou
                     uv[2 * k] = me.texcoords[2 * vi];
                     uv[2 * k + 1] = me.texcoords[2 * vi + 1];
                 }
-                float wbits;
-                // w tags: v0 = original triangle index, v1 = mesh, v2 = alpha cut-out flag
-                int tag = (k == 0) ? (int)t : (k == 1 ? m : (me.albedo_tex >= 0 ? 1 : 0));
-                std::memcpy(&wbits, &tag, 4);
-                tri[3 * t + k] = make_float4(wv[3 * vi], wv[3 * vi + 1], wv[3 * vi + 2], wbits);
-                nrm[3 * t + k] = make_float4(wn[3 * vi], wn[3 * vi + 1], wn[3 * vi + 2], 0.0f);
-                for (int a = 0; a < 3; ++a) {
-                    lo[a] = std::min(lo[a], wv[3 * vi + a]);
-                    hi[a] = std::max(hi[a], wv[3 * vi + a]);
-                }
+                gi[k] = voff + vi;
             }
-            for (int a = 0; a < 3; ++a) {
-                float c = 0.5f * (lo[a] + hi[a]);
-                cmin[a] = std::min(cmin[a], c);
-                cmax[a] = std::max(cmax[a], c);
-            }
+            G.tidx.push_back(make_int4(gi[0], gi[1], gi[2], m));
             if (any_tex) {
-                uvs[2 * t] = make_float4(uv[0], uv[1], uv[2], uv[3]);
-                uvs[2 * t + 1] = make_float4(uv[4], uv[5], 0.0f, 0.0f);
+                G.uvs.push_back(make_float4(uv[0], uv[1], uv[2], uv[3]));
+                G.uvs.push_back(make_float4(uv[4], uv[5], 0.0f, 0.0f));
             }
         }
     }
+    std::vector<float4> tri, nrm;
+    float cmin[3], cmax[3];
+    bake_scene(G, tri, nrm, cmin, cmax);
 
     pt_renderer* r = new pt_renderer();
     // A/B switch for the wide trace workgroups (tools/ab.sh runs one library with and without)
@@ -1172,73 +1403,58 @@ int pt_create(const pt_scene* scene, const pt_options* options, pt_renderer** ou
                     "upload texels");
         }
     }
+    r->builder = opt.bvh_builder == PT_BVH_LBVH   ? kBuilderLBVH
+                 : opt.bvh_builder == PT_BVH_PLOC ? kBuilderPLOC
+                 : opt.bvh_builder == PT_BVH_SAH  ? kBuilderSAH
+                                                  : kBuilderSAHGPU;
+    r->geom = std::move(G);
+    r->mats = mats;
+    {
+        const int rc = need_tex_kernels(r);
+        if (rc != PT_OK) return cleanup_fail(rc);
+    }
+    r->staged.resize((size_t)std::max(0, scene->n_meshes));
     if (ntri > 0) {
-        float4 *d_tri_orig = nullptr, *d_nrm_orig = nullptr, *d_uv_orig = nullptr;
-        if (any_tex) {
-            PT_HIPC(hipMalloc(&r->d_tuv, sizeof(float4) * 2 * ntri), "hipMalloc tuv");
-            PT_HIPC(hipMalloc(&d_uv_orig, sizeof(float4) * 2 * ntri), "hipMalloc uv_orig");
-            PT_HIPC(hipMemcpyAsync(d_uv_orig, uvs.data(), sizeof(float4) * 2 * ntri, hipMemcpyHostToDevice,
-                                   r->stream),
-                    "upload uv");
-        }
+        if (any_tex) PT_HIPC(hipMalloc(&r->d_tuv, sizeof(float4) * 2 * ntri), "hipMalloc tuv");
         PT_HIPC(hipMalloc(&r->d_isect, sizeof(float4) * 3 * ntri), "hipMalloc isect");
         PT_HIPC(hipMalloc(&r->d_shade, sizeof(float4) * 4 * ntri), "hipMalloc shade");
         PT_HIPC(hipMalloc(&r->d_nodes, sizeof(BNode4) * std::max<size_t>(1, ntri)), "hipMalloc nodes");
-        PT_HIPC(hipMalloc(&d_tri_orig, sizeof(float4) * 3 * ntri), "hipMalloc tri_orig");
-        PT_HIPC(hipMalloc(&d_nrm_orig, sizeof(float4) * 3 * ntri), "hipMalloc nrm_orig");
-        PT_HIPC(hipMemcpyAsync(d_tri_orig, tri.data(), sizeof(float4) * 3 * ntri, hipMemcpyHostToDevice, r->stream),
-                "upload tri");
-        PT_HIPC(hipMemcpyAsync(d_nrm_orig, nrm.data(), sizeof(float4) * 3 * ntri, hipMemcpyHostToDevice, r->stream),
-                "upload nrm");
-        BuildInput in;
-        in.tri_orig = d_tri_orig;
-        in.nrm_orig = d_nrm_orig;
-        in.uv_orig = d_uv_orig;
-        in.n = (int)ntri;
-        // AUTO: the binned-SAH tree (fewest node visits of the builders, DESIGN.md §5), built on the
-        // GPU; every peer of a multi-device renderer builds its own on its own device
-        in.builder = opt.bvh_builder == PT_BVH_LBVH   ? kBuilderLBVH
-                     : opt.bvh_builder == PT_BVH_PLOC ? kBuilderPLOC
-                     : opt.bvh_builder == PT_BVH_SAH  ? kBuilderSAH
-                                                      : kBuilderSAHGPU;
-        in.tri_host = tri.data();
-        for (int a = 0; a < 3; ++a) {
-            in.cmin[a] = cmin[a];
-            in.cmax[a] = cmax[a];
-        }
         BuildOutput bo;
         bo.nodes = r->d_nodes;
         bo.isect = r->d_isect;
         bo.shade = r->d_shade;
         bo.tuv = r->d_tuv;
-        float ms = 0.0f;
-        hipError_t be = lbvh_build(in, bo, r->stream, &ms);
-        (void)hipStreamSynchronize(r->stream);
-        (void)hipFree(d_tri_orig);
-        (void)hipFree(d_nrm_orig);
-        if (d_uv_orig) (void)hipFree(d_uv_orig);
-        if (be != hipSuccess) return cleanup_fail(hip_fail(be, "lbvh_build"));
-        r->bvh_ms = ms;
+        int rc = build_tree(r, tri, nrm, cmin, cmax, bo);
+        if (rc != PT_OK) return cleanup_fail(rc);
         r->bvh_nodes = bo.n_nodes;
         r->bvh_depth = bo.depth;
+        r->level_base = bo.level_base;
         // a traversal holds at most 3 stack entries per BVH4 level; the smallest traversal stack
         // (kMinTraversalStack) must hold them, or rays could lose subtrees
         if (3 * bo.depth > kMinTraversalStack)
             return cleanup_fail(fail(PT_ERR_INVALID, "pt_create: BVH too deep for the traversal stack (depth " +
                                                          std::to_string(bo.depth) + ")"));
-        // lit table: the cells of every leaf-ordered triangle (the bits follow the lights, lit_prepare)
-        std::vector<float4> isect_host(3 * ntri);
-        PT_HIPC(hipMemcpy(isect_host.data(), r->d_isect, sizeof(float4) * 3 * ntri, hipMemcpyDeviceToHost),
-                "download isect");
-        std::vector<uint32_t> lit_words_host;
-        if (lit_subdivide(isect_host.data(), (int)ntri, lit_words_host, &r->lit_cells, &r->lit_diag)) {
-            r->lit_words = (r->lit_cells + 31) / 32;
-            PT_HIPC(hipMalloc(&r->d_lit_tri, sizeof(uint32_t) * ntri), "hipMalloc lit table");
-            PT_HIPC(hipMalloc(&r->d_lit_bits, sizeof(uint32_t) * (size_t)r->lit_words * kLitMaxLights),
-                    "hipMalloc lit table");
-            PT_HIPC(hipMemcpy(r->d_lit_tri, lit_words_host.data(), sizeof(uint32_t) * ntri, hipMemcpyHostToDevice),
-                    "upload lit table");
+        // retained on the device for k_rebake, and the SAH cost of the tree as built
+        const size_t nv = r->geom.verts.size();
+        PT_HIPC(hipMalloc(&r->d_overts, sizeof(float4) * std::max<size_t>(1, nv)), "hipMalloc vertices");
+        PT_HIPC(hipMalloc(&r->d_onorms, sizeof(float4) * std::max<size_t>(1, nv)), "hipMalloc normals");
+        PT_HIPC(hipMalloc(&r->d_tidx, sizeof(int4) * ntri), "hipMalloc indices");
+        PT_HIPC(hipMalloc(&r->d_rmesh, sizeof(RefitMesh) * (size_t)std::max(1, r->nmesh)), "hipMalloc mesh records");
+        PT_HIPC(hipMalloc(&r->d_sah_part, sizeof(double) * ((size_t)sah_partial_blocks((int)ntri) + 1)),
+                "hipMalloc SAH partials");
+        PT_HIPC(hipEventCreate(&r->geom_ev[0]), "hipEventCreate");
+        PT_HIPC(hipEventCreate(&r->geom_ev[1]), "hipEventCreate");
+        if (nv > 0) {
+            PT_HIPC(hipMemcpy(r->d_overts, r->geom.verts.data(), sizeof(float4) * nv, hipMemcpyHostToDevice),
+                    "upload vertices");
+            PT_HIPC(hipMemcpy(r->d_onorms, r->geom.norms.data(), sizeof(float4) * nv, hipMemcpyHostToDevice),
+                    "upload normals");
         }
+        PT_HIPC(hipMemcpy(r->d_tidx, r->geom.tidx.data(), sizeof(int4) * ntri, hipMemcpyHostToDevice),
+                "upload indices");
+        if ((rc = sah_cost_now(r, true)) != PT_OK) return cleanup_fail(rc);
+        // lit table: the cells of every leaf-ordered triangle (the bits follow the lights, lit_prepare)
+        if ((rc = lit_resubdivide(r)) != PT_OK) return cleanup_fail(rc);
     }
     PT_HIPC(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
 #undef PT_HIPC
@@ -1297,6 +1513,13 @@ int pt_destroy(pt_renderer* r) {
     if (r->d_lights) (void)hipFree(r->d_lights);
     if (r->d_lit_tri) (void)hipFree(r->d_lit_tri);
     if (r->d_lit_bits) (void)hipFree(r->d_lit_bits);
+    if (r->d_overts) (void)hipFree(r->d_overts);
+    if (r->d_onorms) (void)hipFree(r->d_onorms);
+    if (r->d_tidx) (void)hipFree(r->d_tidx);
+    if (r->d_rmesh) (void)hipFree(r->d_rmesh);
+    if (r->d_sah_part) (void)hipFree(r->d_sah_part);
+    for (hipEvent_t e : r->geom_ev)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : r->lit_ev)
         if (e) (void)hipEventDestroy(e);
     if (r->d_frame) (void)hipFree(r->d_frame);
@@ -1442,6 +1665,160 @@ int pt_set_kernel(pt_renderer* r, int32_t kernel) {
     r->kernel = kernel;
     for (pt_renderer* p : r->peers) p->kernel = kernel;
     cancel_look_ahead(r);
+    return PT_OK;
+}
+
+int pt_set_mesh_transform(pt_renderer* r, int32_t mesh, const float model_matrix[16]) {
+    if (!r || !model_matrix) return fail(PT_ERR_INVALID, "pt_set_mesh_transform: NULL");
+    if (mesh < 0 || mesh >= r->nmesh) return fail(PT_ERR_INVALID, "pt_set_mesh_transform: mesh out of range");
+    for (pt_renderer* p : r->peers) {
+        const int rc = pt_set_mesh_transform(p, mesh, model_matrix);
+        if (rc) return rc;
+    }
+    pt_renderer::StagedMesh& sm = r->staged[(size_t)mesh];
+    std::memcpy(sm.model, model_matrix, sizeof sm.model);
+    sm.has_model = true;
+    r->geom_staged = true;
+    return PT_OK;
+}
+
+int pt_set_mesh_vertices(pt_renderer* r, int32_t mesh, const float* vertices, const float* normals) {
+    if (!r || !vertices) return fail(PT_ERR_INVALID, "pt_set_mesh_vertices: NULL");
+    if (mesh < 0 || mesh >= r->nmesh) return fail(PT_ERR_INVALID, "pt_set_mesh_vertices: mesh out of range");
+    if (normals && !r->geom.has_normals[(size_t)mesh])
+        return fail(PT_ERR_INVALID, "pt_set_mesh_vertices: the mesh was created without normals");
+    for (pt_renderer* p : r->peers) {
+        const int rc = pt_set_mesh_vertices(p, mesh, vertices, normals);
+        if (rc) return rc;
+    }
+    const size_t nv = (size_t)(r->geom.voff[(size_t)mesh + 1] - r->geom.voff[(size_t)mesh]);
+    pt_renderer::StagedMesh& sm = r->staged[(size_t)mesh];
+    sm.verts.assign(vertices, vertices + 3 * nv);
+    sm.has_verts = true;
+    if (normals) {
+        sm.norms.assign(normals, normals + 3 * nv);
+        sm.has_norms = true;
+    }
+    r->geom_staged = true;
+    return PT_OK;
+}
+
+int pt_commit_geometry(pt_renderer* r, int32_t how) {
+    if (!r) return fail(PT_ERR_INVALID, "pt_commit_geometry: NULL renderer");
+    if (how != PT_GEOM_REFIT && how != PT_GEOM_REBUILD)
+        return fail(PT_ERR_INVALID, "pt_commit_geometry: how must be PT_GEOM_REFIT or PT_GEOM_REBUILD");
+    if (!r->geom_staged) return PT_OK;
+    // every peer applies the same staged changes (the setters forwarded them) on its own device
+    for (pt_renderer* p : r->peers) {
+        const int rc = pt_commit_geometry(p, how);
+        if (rc) return rc;
+    }
+    PT_HIP(hipSetDevice(r->device), "hipSetDevice");
+    // the kernels already enqueued read the arrays about to be overwritten: stop a speculative
+    // batch, then wait for every stream
+    cancel_look_ahead(r, true);
+    PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
+    for (int k = 1; k < pt_renderer::kMaxWFStreams; ++k)
+        if (r->xstream[k]) PT_HIP(hipStreamSynchronize(r->xstream[k]), "hipStreamSynchronize");
+    if (r->dl_stream) PT_HIP(hipStreamSynchronize(r->dl_stream), "hipStreamSynchronize");
+    int rc = collect_pending(r);
+    if (rc) return rc;
+
+    // staged -> retained host copy; the dirty meshes' records for k_rebake
+    GeomHost& G = r->geom;
+    std::vector<RefitMesh> rm((size_t)std::max(1, r->nmesh));
+    for (int m = 0; m < r->nmesh; ++m) {
+        pt_renderer::StagedMesh& sm = r->staged[(size_t)m];
+        const size_t v0 = (size_t)G.voff[(size_t)m], nv = (size_t)G.voff[(size_t)m + 1] - v0;
+        if (sm.has_model) std::memcpy(&G.model[16 * (size_t)m], sm.model, sizeof sm.model);
+        for (size_t v = 0; sm.has_verts && v < nv; ++v)
+            G.verts[v0 + v] = make_float4(sm.verts[3 * v], sm.verts[3 * v + 1], sm.verts[3 * v + 2], 0.0f);
+        for (size_t v = 0; sm.has_norms && v < nv; ++v)
+            G.norms[v0 + v] = make_float4(sm.norms[3 * v], sm.norms[3 * v + 1], sm.norms[3 * v + 2], 0.0f);
+        RefitMesh& d = rm[(size_t)m];
+        std::memcpy(d.m, &G.model[16 * (size_t)m], sizeof d.m);
+        d.dirty = (sm.has_model || sm.has_verts) ? 1 : 0;
+        d.normal_mode = G.normal_mode(m);
+        if (sm.has_model) G.normal_rows(m, &r->mats[(size_t)kMatStride * (size_t)m]);
+        d.pad[0] = d.pad[1] = 0;
+        if (r->ntri > 0 && nv > 0 && sm.has_verts)
+            PT_HIP(hipMemcpy(r->d_overts + v0, &G.verts[v0], sizeof(float4) * nv, hipMemcpyHostToDevice),
+                   "upload vertices");
+        if (r->ntri > 0 && nv > 0 && sm.has_norms)
+            PT_HIP(hipMemcpy(r->d_onorms + v0, &G.norms[v0], sizeof(float4) * nv, hipMemcpyHostToDevice),
+                   "upload normals");
+        sm = pt_renderer::StagedMesh();
+    }
+    r->geom_staged = false;
+    r->geom_version++;
+    r->geom_commits++;
+    r->geom_commit_ms = 0.0;
+    if (r->ntri <= 0) {  // nothing to trace: the retained scene alone changed
+        if (how == PT_GEOM_REBUILD) r->geom_rebuilds++;
+        else r->geom_refits++;
+        return PT_OK;
+    }
+
+    PT_HIP(hipMemcpy(r->d_mats, r->mats.data(), sizeof(float4) * r->mats.size(), hipMemcpyHostToDevice), "upload mats");
+    if ((rc = need_tex_kernels(r)) != PT_OK) return rc;
+    // refit: re-bake the dirty meshes' records, every node box bottom-up, the SAH cost
+    PT_HIP(hipMemcpy(r->d_rmesh, rm.data(), sizeof(RefitMesh) * rm.size(), hipMemcpyHostToDevice), "upload mesh records");
+    PT_HIP(hipEventRecord(r->geom_ev[0], r->stream), "hipEventRecord");
+    PT_HIP(refit_rebake(r->d_rmesh, r->d_overts, r->d_onorms, r->d_tidx, r->ntri, r->d_isect, r->d_shade, r->stream),
+           "k_rebake");
+    PT_HIP(refit_levels(r->d_nodes, r->d_isect, r->level_base, r->stream), "k_refit_level");
+    if ((rc = sah_cost_now(r, false, r->geom_ev[1])) != PT_OK) return rc;
+    float ms = 0.0f;
+    PT_HIP(hipEventElapsedTime(&ms, r->geom_ev[0], r->geom_ev[1]), "hipEventElapsedTime");
+    r->geom_commit_ms = ms;
+
+    // rebuild: the create path's bake and build into temporary buffers, swapped in on success
+    int rebuild_rc = PT_OK;
+    std::string rebuild_msg;
+    if (how == PT_GEOM_REBUILD) {
+        const size_t ntri = (size_t)r->ntri;
+        std::vector<float4> tri, nrm;
+        float cmin[3], cmax[3];
+        bake_scene(G, tri, nrm, cmin, cmax);
+        BuildOutput bo;
+        bo.nodes = nullptr;
+        bo.isect = bo.shade = bo.tuv = nullptr;
+        hipError_t e = hipMalloc(&bo.nodes, sizeof(BNode4) * std::max<size_t>(1, ntri));
+        if (e == hipSuccess) e = hipMalloc(&bo.isect, sizeof(float4) * 3 * ntri);
+        if (e == hipSuccess) e = hipMalloc(&bo.shade, sizeof(float4) * 4 * ntri);
+        if (e == hipSuccess && r->d_tuv) e = hipMalloc(&bo.tuv, sizeof(float4) * 2 * ntri);
+        float bms = 0.0f;
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            rebuild_rc = hip_fail(e, "hipMalloc rebuild buffers");
+        } else {
+            rebuild_rc = build_tree(r, tri, nrm, cmin, cmax, bo, &bms);
+        }
+        if (rebuild_rc == PT_OK && 3 * bo.depth > kMinTraversalStack)
+            rebuild_rc = fail(PT_ERR_INVALID, "pt_commit_geometry: the rebuilt BVH is too deep for the traversal stack (depth " +
+                                                  std::to_string(bo.depth) + "); the refitted tree stays in force");
+        if (rebuild_rc == PT_OK) {
+            std::swap(r->d_nodes, bo.nodes);
+            std::swap(r->d_isect, bo.isect);
+            std::swap(r->d_shade, bo.shade);
+            std::swap(r->d_tuv, bo.tuv);
+            r->bvh_nodes = bo.n_nodes;
+            r->bvh_depth = bo.depth;
+            r->level_base = bo.level_base;
+            r->geom_commit_ms += bms;
+        } else {
+            rebuild_msg = g_last_error;
+        }
+        for (void* p : {(void*)bo.nodes, (void*)bo.isect, (void*)bo.shade, (void*)bo.tuv})
+            if (p) (void)hipFree(p);
+        if (rebuild_rc == PT_OK && (rc = sah_cost_now(r, true)) != PT_OK) return rc;
+    }
+    if (how == PT_GEOM_REBUILD && rebuild_rc == PT_OK) r->geom_rebuilds++;
+    else r->geom_refits++;
+
+    // the lit table's cells follow the records in force; its bits are rebuilt by the next call
+    if ((rc = lit_resubdivide(r)) != PT_OK) return rc;
+    if (rebuild_rc != PT_OK) return fail(rebuild_rc, rebuild_msg);
     return PT_OK;
 }
 
@@ -1769,6 +2146,12 @@ int pt_get_stats(pt_renderer* r, pt_stats* out) {
         out->lit_table_bytes = sizeof(uint32_t) * ((size_t)r->ntri + (size_t)r->lit_words * kLitMaxLights);
         out->lit_table_build_ms = r->lit_build_ms;
     }
+    out->geometry_commits = r->geom_commits;
+    out->geometry_refits = r->geom_refits;
+    out->geometry_rebuilds = r->geom_rebuilds;
+    out->geometry_commit_ms = r->geom_commit_ms;
+    out->bvh_sah_cost = r->sah_cost;
+    out->bvh_sah_cost_built = r->sah_cost_built;
     // a multi-device renderer reports the work of all its devices (times are device 0's)
     for (pt_renderer* p : r->peers) {
         pt_stats ps;

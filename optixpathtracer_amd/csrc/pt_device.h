@@ -10,7 +10,7 @@
 //   isect  : float4[3N]         — v0.xyz|orig index, e1.xyz|material, e2.xyz|0  (e = v - v0,
 //                                  the same fp32 subtraction the oracle performs)
 //   shade  : float4[4N]         — v1.xyz|n0.x, v2.xyz|n0.y, n0.z n1.xyz, n2.xyz|0
-//   mats   : float4[3M]         — albedo.xyz|metallic, roughness|has_normals|texture ids, ... (kMatStride)
+//   mats   : float4[6M]         — albedo.xyz|metallic, roughness|normal mode|texture ids, ... (kMatStride)
 // Leaves reference up to 4 consecutive triangles (a BVH subtree is a contiguous range of the
 // leaf-ordered triangles, so no index indirection is needed).
 #pragma once
@@ -45,10 +45,22 @@ struct DevScene {
     int n_lds;
 };
 
-// Material record (3 x float4 per mesh):
-//   [0] albedo.rgb | metallic     [1] roughness | has_normals | albedo_tex | normal_tex
+// Material record (6 x float4 per mesh):
+//   [0] albedo.rgb | metallic     [1] roughness | normal mode | albedo_tex | normal_tex
 //   [2] metal_rough_tex | any texture | 0 | 0          (texture ids as int bits, -1 = none)
-constexpr int kMatStride = 3;
+//   [3..5] rows 0..2 of the model matrix (kNormalObject meshes only)
+// Normal mode.  The reference interpolates the object-space vertex normals and takes the result
+// through modelMatrix * vec4(Ns, 0) (GetNormal, devicePrograms.cu:83-117).  Where the matrix's 3x3
+// part only permutes and negates (the identity, any translation), transforming the vertex normals
+// once at bake time gives the same bits, and the shade records hold world-space normals
+// (kNormalBaked).  For any other matrix the two orders round differently, so the records keep the
+// object-space normals and reconstruct applies the matrix after the interpolation (kNormalObject).
+// Only the TEX instantiations of the kernels carry that code (like the texture sampling, it stays
+// out of the register budget of the plain ones): a scene with such a mesh runs them, textured or
+// not (pt_capi.cpp gives it a texinfo array, which is what selects them).
+constexpr int kMatStride = 6;
+constexpr float kNormalNone = 0.0f, kNormalBaked = 1.0f, kNormalObject = 2.0f;
+PT_HD float mat_row_dir(float4 row, f3 n) { return (row.x * n.x + row.y * n.y) + (row.z * n.z + row.w * 0.0f); }
 
 struct DevLight {
     float px, py, pz, cr, cg, cb;
@@ -865,7 +877,14 @@ __device__ __forceinline__ void reconstruct(const DevScene& S, const Hit& h, f3 
     const float u = h.u, v = h.v;
     float w = 1.0f - u - v;
     f3 Ns = mk(w * n0.x + u * n1.x + v * n2.x, w * n0.y + u * n1.y + v * n2.y, w * n0.z + u * n1.z + v * n2.z);
-    if (M1.y != 0.0f) Ns = normalize(Ns);  // has normals: normalize(modelMatrix * vec4(Ns, 0))
+    if (M1.y != kNormalNone) {  // has normals: normalize(modelMatrix * vec4(Ns, 0))
+        if (TEX && M1.y == kNormalObject) {  // mat4_mul_vec4's order, row by row
+            const float4 R0 = S.mats[kMatStride * mi + 3], R1 = S.mats[kMatStride * mi + 4],
+                         R2 = S.mats[kMatStride * mi + 5];
+            Ns = mk(mat_row_dir(R0, Ns), mat_row_dir(R1, Ns), mat_row_dir(R2, Ns));
+        }
+        Ns = normalize(Ns);
+    }
     if (dot(wo_w, Ng) < 0.0f) Ng = -Ng;
     Ng = normalize(Ng);
     if (dot(Ng, Ns) < 0.0f) Ns = -Ns;

@@ -52,7 +52,18 @@ struct BuildOutput {
     float4* tuv;    // 2n or NULL
     int n_nodes;    // written by lbvh_build
     int depth;      // BVH4 levels
+    // first node of every BVH4 level (breadth-first numbering) and, last, n_nodes: level l is
+    // nodes level_base[l] .. level_base[l + 1] - 1 (refit_levels walks them deepest first)
+    std::vector<int> level_base;
 };
+
+// The collapse's SAH constants (pt_build.hip k_sah_dp; refit's cost reduction uses the same).  With
+// the dual traversal step (pt_device.h) a triangle test overlaps a node visit, hence cTri < cNode.
+#ifndef PT_SAH_CTRI
+#define PT_SAH_CTRI 0.5f
+#endif
+constexpr float kSahCNode = 1.0f;
+constexpr float kSahCTri = PT_SAH_CTRI;
 
 // GPU LBVH build (Morton codes -> radix sort -> Karras 2012 hierarchy -> AABBs from a sparse
 // table over the sorted leaves).  Replaces optixAccelBuild (OptixRenderer.cpp:306-456).
@@ -125,6 +136,26 @@ hipError_t launch_trace(const DevScene& S, const float* d_rays, int n, int* d_pr
 bool lit_subdivide(const float4* isect, int ntri, std::vector<uint32_t>& words, uint32_t* cells, float* diagonal);
 hipError_t lit_build(const DevScene& S, const uint32_t* tri_words, uint32_t cells, uint32_t words,
                      const DevLight* lights, int n_lights, uint32_t* bits, float diag, hipStream_t stream);
+
+// Geometry updates (pt_refit.hip).  RefitMesh: what k_rebake needs of one mesh.
+struct RefitMesh {
+    float m[16];      // model matrix, column-major
+    int dirty;        // re-bake this mesh's triangles
+    int normal_mode;  // 0: its normals bake to zeros; 1: transformed here (kNormalBaked); 2: kept in
+                      // object space (kNormalObject, pt_device.h)
+    int pad[2];
+};
+// Re-bakes the records of the dirty meshes' triangles in place (isect / shade, leaf order).  overts /
+// onorms: object-space vertices and normals of all meshes; tidx: per original triangle, its three
+// indices into them.
+hipError_t refit_rebake(const RefitMesh* meshes, const float4* overts, const float4* onorms, const int4* tidx, int n,
+                        float4* isect, float4* shade, hipStream_t stream);
+// Recomputes every node box from the triangle records, one launch per level, deepest first.
+hipError_t refit_levels(BNode4* nodes, const float4* isect, const std::vector<int>& level_base, hipStream_t stream);
+// SAH cost reduction: partial[0 .. sah_partial_blocks(n) - 1] = per-block fp64 sums (to be added in
+// block order), partial[sah_partial_blocks(n)] = the root's half area.
+int sah_partial_blocks(int n_nodes);
+hipError_t sah_partial_launch(const BNode4* nodes, int n_nodes, double* partial, hipStream_t stream);
 
 // Progressive view buffer (pt_display.hip).
 hipError_t display_fill(float* p, size_t n, float v, hipStream_t stream);

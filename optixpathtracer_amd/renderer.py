@@ -9,6 +9,7 @@ blend (`Renderer/OptixView.cpp:201-255`).
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -91,6 +92,7 @@ class OptixRenderer:
         # ptxPath is accepted for signature compatibility and ignored (no PTX on gfx950).
         self.lib = load()
         self.model = model
+        self._caller_model = model
         self._binding = _SceneBinding(model)
         opts = capi.pt_options()
         opts.device = int(device)
@@ -203,6 +205,53 @@ class OptixRenderer:
         """Time every wavefront trace launch and every launch of the bounce's dominant shading
         kernel with its own HIP event pair (pt_stats trace_kernel_* / shade_kernel_*)."""
         check(self.lib.pt_set_kernel_timing(self.h, 1 if enable else 0), "pt_set_kernel_timing")
+
+    # -- geometry updates (staged, then committed) ----------------------------------------------
+    def _mesh_index(self, mesh: int, what: str) -> int:
+        mesh = int(mesh)
+        if not 0 <= mesh < len(self.model.meshes):
+            raise capi.PTError(f"{what}: mesh {mesh} out of range", capi.PT_ERR_INVALID)
+        return mesh
+
+    def _replace_mesh(self, mesh: int, **kw) -> None:
+        # self.model follows with copies: the caller's Scene, Mesh and arrays are left alone
+        if self.model is self._caller_model:
+            self.model = dataclasses.replace(self.model, meshes=list(self.model.meshes))
+        self.model.meshes[mesh] = dataclasses.replace(self.model.meshes[mesh], **kw)
+
+    def set_mesh_transform(self, mesh: int, model) -> None:
+        """pt_set_mesh_transform: stage a new column-major model matrix (16 floats) for a mesh; it
+        takes effect at commit_geometry().  self.model follows, so OracleScene(r.model) renders
+        the geometry that the next commit puts in force."""
+        mesh = self._mesh_index(mesh, "set_mesh_transform")
+        m = _f32(model).reshape(16).copy()
+        check(self.lib.pt_set_mesh_transform(self.h, mesh, fptr(m)), "pt_set_mesh_transform")
+        self._replace_mesh(mesh, model=m)
+
+    def set_mesh_vertices(self, mesh: int, vertices, normals=None) -> None:
+        """pt_set_mesh_vertices: stage new object-space vertices (V, 3) and, unless None, normals
+        (V, 3; None keeps the current ones) for a mesh; topology and texcoords stay."""
+        mesh = self._mesh_index(mesh, "set_mesh_vertices")
+        cur = self.model.meshes[mesh]
+        v = _f32(vertices).reshape(-1, 3).copy()
+        if v.shape != np.asarray(cur.vertices).shape:
+            raise capi.PTError("set_mesh_vertices: the vertex count cannot change", capi.PT_ERR_INVALID)
+        n = None
+        if normals is not None:
+            n = _f32(normals).reshape(-1, 3).copy()
+            if n.shape != v.shape:
+                raise capi.PTError("set_mesh_vertices: normals must match the vertices", capi.PT_ERR_INVALID)
+        check(self.lib.pt_set_mesh_vertices(self.h, mesh, fptr(v), fptr(n) if n is not None else None),
+              "pt_set_mesh_vertices")
+        self._replace_mesh(mesh, vertices=v, **({} if n is None else {"normals": n}))
+
+    def commit_geometry(self, how: str = "refit") -> None:
+        """pt_commit_geometry: put the staged mesh changes in force, by a BVH refit ("refit") or a
+        rebuild with the renderer's builder ("rebuild").  Synchronous; nothing staged is a no-op."""
+        modes = {"refit": capi.PT_GEOM_REFIT, "rebuild": capi.PT_GEOM_REBUILD}
+        if how not in modes:
+            raise capi.PTError(f"commit_geometry: how must be 'refit' or 'rebuild', not {how!r}", capi.PT_ERR_INVALID)
+        check(self.lib.pt_commit_geometry(self.h, modes[how]), "pt_commit_geometry")
 
     # -- headless progressive view (OptixView accumulation on the device) -------------------
     def display_reset(self, max_samples: int = -1) -> None:
