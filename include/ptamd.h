@@ -196,6 +196,13 @@ typedef struct pt_stats {
     uint64_t lit_table_bits_set;
     uint64_t lit_table_bytes;
     double lit_table_build_ms;
+    /* occluder candidate table (pt_set_occluder_table): device bytes, entries that name a triangle,
+       device time of the last build (all 0 while the table is not in use), and the NEE tests a
+       shading kernel answered "occluded" from it instead of emitting a shadow ray */
+    uint64_t occluder_table_bytes;
+    uint64_t occluder_table_candidates;
+    double occluder_table_build_ms;
+    uint64_t occluder_table_answers;
     /* geometry updates (pt_commit_geometry): commits that changed something, how many of them ended on
        a refitted and how many on a rebuilt tree, and the device time of the last commit's work (HIP
        events around the re-bake, the level refits and the cost reduction, plus the build's own
@@ -311,6 +318,23 @@ typedef struct pt_lit_table_info {
 } pt_lit_table_info;
 int pt_lit_table_download(pt_renderer* r, pt_lit_table_info* info, uint32_t* tri_words, int64_t tri_bytes,
                           uint32_t* bits, int64_t bits_bytes);
+/* The occluder candidate table: beside the lit table, one int32 per (light, cell), laid out
+ * light * cells + cell, holding -1 or a leaf-order triangle that probably occludes the cell's shadow
+ * rays (the closest hit of the ray from the cell's centroid).  Before a shading kernel emits a shadow
+ * ray the lit table did not answer, it tests that one triangle with the tracer's own arithmetic on
+ * the very ray; a hit is the tracer's answer "occluded" whatever triangle the entry names, so the
+ * ray is dropped and images stay bit-identical.  A wrong entry only costs speed.  < 0: automatic
+ * (the default: on in the Lambert, Default and Layered modes while pt_set_lit_table is in auto too;
+ * a lit table forced on is measured alone), 0: off, > 0: on.  It needs the lit table in use and is
+ * rebuilt with it (lights set, geometry committed).  Without the memory for it the renderer runs
+ * without it. */
+int pt_set_occluder_table(pt_renderer* r, int32_t enable);
+/* Tests: the table for the current lights (built now if stale).  *entries_out = lights * cells, or
+ * 0 while it is not in use; `entries` is filled when not NULL and `bytes` = 4 * *entries_out.
+ * pt_occluder_table_upload replaces the entries until the next rebuild; an entry outside
+ * [-1, triangles) is rejected with PT_ERR_INVALID and nothing is written. */
+int pt_occluder_table_download(pt_renderer* r, int64_t* entries_out, int32_t* entries, int64_t bytes);
+int pt_occluder_table_upload(pt_renderer* r, const int32_t* entries, int64_t bytes);
 
 /* LaunchParams (Renderer/OptiX/LaunchParams.h:9-28) as a C struct: the state one optixLaunch
  * reads.  Same fields and meaning; device pointers where the reference holds device pointers

@@ -149,6 +149,10 @@ class pt_stats(C.Structure):
         ("lit_table_bits_set", C.c_uint64),
         ("lit_table_bytes", C.c_uint64),
         ("lit_table_build_ms", C.c_double),
+        ("occluder_table_bytes", C.c_uint64),
+        ("occluder_table_candidates", C.c_uint64),
+        ("occluder_table_build_ms", C.c_double),
+        ("occluder_table_answers", C.c_uint64),
         ("geometry_commits", C.c_uint64),
         ("geometry_refits", C.c_uint64),
         ("geometry_rebuilds", C.c_uint64),
@@ -217,6 +221,9 @@ SIGNATURES = {
     "pt_set_lit_table": (C.c_int, [_R, C.c_int32]),
     "pt_lit_table_download": (C.c_int, [_R, C.POINTER(pt_lit_table_info), C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_int64]),
+    "pt_set_occluder_table": (C.c_int, [_R, C.c_int32]),
+    "pt_occluder_table_download": (C.c_int, [_R, C.POINTER(C.c_int64), C.c_void_p, C.c_int64]),
+    "pt_occluder_table_upload": (C.c_int, [_R, C.c_void_p, C.c_int64]),
     "pt_render_accumulate": (C.c_int, [_R, C.c_uint32, C.c_uint32, _FP]),
     "pt_set_accum_device_buffer": (C.c_int, [_R, C.c_void_p]),
     "pt_accum_device_ptr": (C.c_void_p, [_R]),

@@ -91,7 +91,7 @@ struct EventPool {
 // [9..13] wave schedule of the trace kernels (pt_stats wave_*) [14] node visits served from LDS
 // [15] items of the timed shading kernel (pt_stats shade_kernel_items) [16] [17] rays and
 // algorithmic bytes of the k_trace_pair launches alone (pt_stats pair_kernel_*).
-constexpr int kCounters = 28;  // [20..26]: trace coherence histogram (pt_get_trace_coherence)
+constexpr int kCounters = 29;  // [20..26]: trace coherence histogram (pt_get_trace_coherence)
 // event pairs held by one renderer before launch_frames retires them (EventPool)
 constexpr size_t kMaxPendingEvents = 4096;
 // the smallest traversal stack of any kernel (pt_device.h stack_capacity: 71 entries for the
@@ -402,6 +402,21 @@ struct pt_renderer {
     bool lit_ev_pending = false;
     double lit_build_ms = 0.0;
     int64_t lit_bits_set = -1;  // of the last build; -1 = not counted yet (pt_get_stats)
+    // occluder candidate table (pt_lit.hip k_occ_build): one int per (light, cell), sized for the
+    // lights in use and rebuilt after the bits whenever they are (occ_prepare; a failed allocation
+    // means the renderer runs without it); pt_occluder_table_upload replaces the entries until then
+    int occ_mode = -1;  // pt_set_occluder_table: < 0 auto, 0 off, > 0 on
+    int* d_occ = nullptr;  // n_lights * lit_cells entries in use
+    size_t occ_cap = 0;    // entries d_occ has room for (grown by occ_prepare)
+    bool occ_alloc_failed = false;  // no memory for it: the renderer runs without (until the cells change)
+    uint32_t occ_built_version = 0;
+    const void* occ_built_lights = nullptr;
+    int occ_built_n = 0;
+    bool occ_active = false;  // this call's launches read the table (make_launch)
+    hipEvent_t occ_ev[2] = {nullptr, nullptr};  // around the last build
+    bool occ_ev_pending = false;
+    double occ_build_ms = 0.0;
+    int64_t occ_candidates = -1;  // entries >= 0 of the last build or upload; -1 = not counted yet
 
     DevScene scene() const {
         DevScene S;
@@ -479,6 +494,8 @@ DevLaunch make_launch(const pt_renderer* r, float* accum, uint32_t frame_base, u
     L.lit_tri = r->lit_active ? r->d_lit_tri : nullptr;
     L.lit_bits = r->d_lit_bits;
     L.lit_words = r->lit_words;
+    L.occ_tab = r->lit_active && r->occ_active ? r->d_occ : nullptr;
+    L.lit_cells = r->lit_cells;
     return L;
 }
 
@@ -502,11 +519,68 @@ bool lit_wanted(const pt_renderer* r) {
     const bool on = r->lit_mode < 0 ? PT_LIT_TABLE != 0 && pays && !r->lit_launch_call : r->lit_mode > 0;
     return on && r->d_lit_tri && r->d_lights && r->n_lights >= 1 && r->n_lights <= kLitMaxLights;
 }
+// The occluder candidate table (pt_lit.hip k_occ_build) rides on the lit table: same cells, same
+// lights, rebuilt right after the bits on the same stream.
+#ifndef PT_OCC_TABLE
+#define PT_OCC_TABLE 1  // auto (pt_set_occluder_table < 0): 1 = on where it pays, 0 = off (A/B builds)
+#endif
+bool occ_wanted(const pt_renderer* r) {
+    // the kernels that carry the test: k_shade_fused<Lambert> and k_shade_a (Default, Layered); it is
+    // compiled out of the Conductor and Dielectric kernels, which would build the table for nothing
+    const bool has_code = r->material_mode == PT_MAT_LAMBERT || r->material_mode == PT_MAT_DEFAULT ||
+                          r->material_mode == PT_MAT_LAYERED;
+    // auto: on in all three -- three interleaved runs per side at 1080p, the slowest run with the table
+    // above the parent's fastest by more than three parent spreads: Lambert +4.8 %, Default +1.3 %
+    // (sphere box; one of its two sets of runs had a noisier parent and missed the bar) and +1.7 %
+    // (atrium), Layered +1.0 %; the textured atrium (Default) neither gains nor loses
+    const bool pays = has_code;
+    // auto follows the lit table's auto only: a caller who forces the lit table on is measuring that
+    // table by itself (one traced ray less per lit answer) and asks for the candidates explicitly
+    const bool on = r->occ_mode < 0 ? PT_OCC_TABLE != 0 && pays && r->lit_mode < 0 : r->occ_mode > 0;
+    return on && has_code && !r->occ_alloc_failed && lit_wanted(r);
+}
+// After the lit bits are current on r->stream (lit_prepare): the candidates for the same lights.
+int occ_prepare(pt_renderer* r) {
+    r->occ_active = occ_wanted(r);
+    if (!r->occ_active) return PT_OK;
+    if (r->occ_built_version == r->lit_version && r->occ_built_lights == r->d_lights && r->occ_built_n == r->n_lights)
+        return PT_OK;
+    const size_t need = (size_t)r->lit_cells * (size_t)r->n_lights;
+    if (need > r->occ_cap) {  // hipFree waits for the batches that still read the old array
+        if (r->d_occ) (void)hipFree(r->d_occ);
+        r->d_occ = nullptr;
+        r->occ_cap = 0;
+        if (hipMalloc(&r->d_occ, sizeof(int) * need) != hipSuccess) {  // not an error: no table
+            (void)hipGetLastError();
+            r->d_occ = nullptr;
+            r->occ_alloc_failed = true;
+            r->occ_active = false;
+            return PT_OK;
+        }
+        r->occ_cap = need;
+    }
+    if (!r->occ_ev[0]) {
+        PT_HIP(hipEventCreate(&r->occ_ev[0]), "hipEventCreate");
+        PT_HIP(hipEventCreate(&r->occ_ev[1]), "hipEventCreate");
+    }
+    PT_HIP(hipEventRecord(r->occ_ev[0], r->stream), "hipEventRecord");
+    PT_HIP(occ_build(r->scene(), r->d_lit_tri, r->lit_cells, r->lit_words, r->d_lights, r->n_lights, r->d_lit_bits,
+                     r->d_occ, r->stream),
+           "occ_build");
+    PT_HIP(hipEventRecord(r->occ_ev[1], r->stream), "hipEventRecord");
+    r->occ_ev_pending = true;
+    r->occ_candidates = -1;
+    r->occ_built_version = r->lit_version;
+    r->occ_built_lights = r->d_lights;
+    r->occ_built_n = r->n_lights;
+    return PT_OK;
+}
 int lit_prepare(pt_renderer* r) {
     r->lit_active = lit_wanted(r);
+    r->occ_active = false;
     if (!r->lit_active) return PT_OK;
     if (r->lit_built_version == r->lit_version && r->lit_built_lights == r->d_lights && r->lit_built_n == r->n_lights)
-        return PT_OK;
+        return occ_prepare(r);
     if (!r->lit_ev[0]) {
         PT_HIP(hipEventCreate(&r->lit_ev[0]), "hipEventCreate");
         PT_HIP(hipEventCreate(&r->lit_ev[1]), "hipEventCreate");
@@ -521,7 +595,7 @@ int lit_prepare(pt_renderer* r) {
     r->lit_built_version = r->lit_version;
     r->lit_built_lights = r->d_lights;
     r->lit_built_n = r->n_lights;
-    return PT_OK;
+    return occ_prepare(r);
 }
 
 // Bytes the wavefront queues of all streams hold now.
@@ -1236,6 +1310,7 @@ int lit_resubdivide(pt_renderer* r) {
     r->lit_cells = cells;
     r->lit_words = words;
     r->lit_diag = diag;
+    r->occ_alloc_failed = false;  // occ_prepare sizes the candidates' array for the new cells
     return PT_OK;
 }
 
@@ -1513,6 +1588,7 @@ int pt_destroy(pt_renderer* r) {
     if (r->d_lights) (void)hipFree(r->d_lights);
     if (r->d_lit_tri) (void)hipFree(r->d_lit_tri);
     if (r->d_lit_bits) (void)hipFree(r->d_lit_bits);
+    if (r->d_occ) (void)hipFree(r->d_occ);
     if (r->d_overts) (void)hipFree(r->d_overts);
     if (r->d_onorms) (void)hipFree(r->d_onorms);
     if (r->d_tidx) (void)hipFree(r->d_tidx);
@@ -1521,6 +1597,8 @@ int pt_destroy(pt_renderer* r) {
     for (hipEvent_t e : r->geom_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : r->lit_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : r->occ_ev)
         if (e) (void)hipEventDestroy(e);
     if (r->d_frame) (void)hipFree(r->d_frame);
     ring_free(r);
@@ -2146,6 +2224,30 @@ int pt_get_stats(pt_renderer* r, pt_stats* out) {
         out->lit_table_bytes = sizeof(uint32_t) * ((size_t)r->ntri + (size_t)r->lit_words * kLitMaxLights);
         out->lit_table_build_ms = r->lit_build_ms;
     }
+    out->occluder_table_answers = c[28];
+    if (r->occ_ev_pending) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, r->occ_ev[0], r->occ_ev[1]) == hipSuccess)
+            r->occ_build_ms = ms;
+        else
+            (void)hipGetLastError();
+        r->occ_ev_pending = false;
+    }
+    // like the lit fields: only while the table is in use and built for the renderer's lights
+    if (occ_wanted(r) && r->d_occ && r->occ_built_version == r->lit_version && r->occ_built_lights == r->d_lights &&
+        r->occ_built_n == r->n_lights) {
+        const size_t ne = (size_t)r->lit_cells * (size_t)r->occ_built_n;
+        if (r->occ_candidates < 0) {
+            std::vector<int> ho(ne);
+            PT_HIP(hipMemcpy(ho.data(), r->d_occ, sizeof(int) * ne, hipMemcpyDeviceToHost), "download occluder table");
+            int64_t n = 0;
+            for (int t : ho) n += t >= 0;
+            r->occ_candidates = n;
+        }
+        out->occluder_table_bytes = sizeof(int) * ne;
+        out->occluder_table_candidates = (uint64_t)r->occ_candidates;
+        out->occluder_table_build_ms = r->occ_build_ms;
+    }
     out->geometry_commits = r->geom_commits;
     out->geometry_refits = r->geom_refits;
     out->geometry_rebuilds = r->geom_rebuilds;
@@ -2180,6 +2282,7 @@ int pt_get_stats(pt_renderer* r, pt_stats* out) {
         out->pair_kernel_bytes += ps.pair_kernel_bytes;
         out->pair_kernel_shadow_rays += ps.pair_kernel_shadow_rays;
         out->lit_table_answers += ps.lit_table_answers;
+        out->occluder_table_answers += ps.occluder_table_answers;
         out->queue_bytes += ps.queue_bytes;
     }
     return PT_OK;
@@ -2511,6 +2614,53 @@ extern "C" int pt_lit_table_download(pt_renderer* r, pt_lit_table_info* info, ui
         if (bits_bytes != (int64_t)(sizeof(uint32_t) * (size_t)r->lit_words * (size_t)r->n_lights))
             return fail(PT_ERR_INVALID, "pt_lit_table_download: bits size mismatch");
         PT_HIP(hipMemcpy(bits, r->d_lit_bits, (size_t)bits_bytes, hipMemcpyDeviceToHost), "download lit table");
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_set_occluder_table(pt_renderer* r, int32_t enable) {
+    if (!r) return fail(PT_ERR_INVALID, "pt_set_occluder_table: NULL");
+    const int mode = enable < 0 ? -1 : (enable > 0 ? 1 : 0);
+    r->occ_mode = mode;  // the images do not depend on it: frames rendered ahead stay valid
+    for (pt_renderer* p : r->peers) p->occ_mode = mode;
+    return PT_OK;
+}
+
+// The table for the renderer's state, built now if it is stale; *entries_out = lights * cells, 0 while
+// it is not in use.  PT_ERR_INVALID for a buffer of another size.
+extern "C" int pt_occluder_table_download(pt_renderer* r, int64_t* entries_out, int32_t* entries, int64_t bytes) {
+    if (!r || !entries_out) return fail(PT_ERR_INVALID, "pt_occluder_table_download: NULL");
+    PT_HIP(hipSetDevice(r->device), "hipSetDevice");
+    int rc = lit_prepare(r);
+    if (rc) return rc;
+    *entries_out = r->occ_active ? (int64_t)r->lit_cells * (int64_t)r->n_lights : 0;
+    if (!r->occ_active || !entries) return PT_OK;
+    if (bytes != (int64_t)sizeof(int32_t) * *entries_out)
+        return fail(PT_ERR_INVALID, "pt_occluder_table_download: size mismatch");
+    PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
+    PT_HIP(hipMemcpy(entries, r->d_occ, (size_t)bytes, hipMemcpyDeviceToHost), "download occluder table");
+    return PT_OK;
+}
+
+// Replaces the entries (lights * cells of them) until the next rebuild.  Every entry must be -1 or a
+// leaf-order triangle index of the scene: anything else is rejected, nothing is written.
+extern "C" int pt_occluder_table_upload(pt_renderer* r, const int32_t* entries, int64_t bytes) {
+    if (!r || !entries) return fail(PT_ERR_INVALID, "pt_occluder_table_upload: NULL");
+    PT_HIP(hipSetDevice(r->device), "hipSetDevice");
+    int rc = pt_synchronize(r);  // no batch in flight reads the entries while they change
+    if (rc) return rc;
+    if ((rc = lit_prepare(r)) != PT_OK) return rc;
+    if (!r->occ_active) return fail(PT_ERR_INVALID, "pt_occluder_table_upload: the table is not in use");
+    const int64_t n = (int64_t)r->lit_cells * (int64_t)r->n_lights;
+    if (bytes != (int64_t)sizeof(int32_t) * n) return fail(PT_ERR_INVALID, "pt_occluder_table_upload: size mismatch");
+    for (int64_t i = 0; i < n; ++i)
+        if (entries[i] < -1 || entries[i] >= r->ntri)
+            return fail(PT_ERR_INVALID, "pt_occluder_table_upload: entry out of range");
+    PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");  // the build above, if any
+    PT_HIP(hipMemcpy(r->d_occ, entries, (size_t)bytes, hipMemcpyHostToDevice), "upload occluder table");
+    r->occ_candidates = -1;
+    for (pt_renderer* p : r->peers) {
+        if ((rc = pt_occluder_table_upload(p, entries, bytes)) != PT_OK) return rc;
     }
     return PT_OK;
 }

@@ -99,6 +99,10 @@ struct DevLaunch {
     const uint32_t* lit_tri;
     const uint32_t* lit_bits;
     uint32_t lit_words;
+    // occluder candidate table (pt_lit.hip k_occ_build): occ_tab[light * lit_cells + cell] = -1 or a
+    // leaf-order triangle the shading kernels test before they emit a shadow ray; NULL = not in use
+    const int* occ_tab;
+    uint32_t lit_cells;
 };
 constexpr int kDebugMaxBounces = 64;
 constexpr int kDebugRecordFloats = 22;  // ptamd.h pt_debug_bounce

@@ -136,6 +136,10 @@ hipError_t launch_trace(const DevScene& S, const float* d_rays, int n, int* d_pr
 bool lit_subdivide(const float4* isect, int ntri, std::vector<uint32_t>& words, uint32_t* cells, float* diagonal);
 hipError_t lit_build(const DevScene& S, const uint32_t* tri_words, uint32_t cells, uint32_t words,
                      const DevLight* lights, int n_lights, uint32_t* bits, float diag, hipStream_t stream);
+// The occluder candidate table (pt_lit.hip k_occ_build): occ[light * cells + cell] = -1 or a
+// leaf-order triangle that probably occludes the cell's shadow rays; runs after lit_build on `stream`.
+hipError_t occ_build(const DevScene& S, const uint32_t* tri_words, uint32_t cells, uint32_t words,
+                     const DevLight* lights, int n_lights, const uint32_t* bits, int* occ, hipStream_t stream);
 
 // Geometry updates (pt_refit.hip).  RefitMesh: what k_rebake needs of one mesh.
 struct RefitMesh {

@@ -1,5 +1,6 @@
 // pt_lit.hip — builds the lit table (pt_lit.h): the per-triangle subdivision on the host at
-// pt_create, the (light, cell) bits on the GPU whenever the lights change.
+// pt_create, the (light, cell) bits on the GPU whenever the lights change, and after them the
+// occluder candidate of every cell the bits leave to the tracer (k_occ_build).
 #include "pt_internal.h"
 #include "pt_lit.h"
 
@@ -122,7 +123,87 @@ __global__ __launch_bounds__(kLitBlock) void k_lit_build(DevScene S, const uint3
     atomicOr(&bits[(size_t)li * words + (cell >> 5)], 1u << (cell & 31));
 }
 
+// The occluder candidate table: one int per (light, cell), laid out light * cells + cell,
+// -1 or the leaf-order index of a triangle that probably occludes the cell's shadow rays.  It is a
+// hint: the shading kernels test the named triangle with the tracer's own tri_test + tri_accept on the
+// very ray they would emit, and a passing test is the tracer's "occluded" for ANY triangle (the BVH's
+// boxes hold the triangle's padded box, so the any-hit walk reaches it or stops earlier at another
+// hit).  A wrong or stale entry costs speed only; the one invariant is -1 <= entry < ntri.
+// The candidate is the closest hit of the shadow ray from the cell's centroid, in plain fp32 and with
+// no margin.  A cell with its lit bit set, a triangle without cells, a light beyond kLitMaxCoord or not
+// more than kLitDelta above the plane get -1, and so does a cut-out triangle (E2.w != 0), so the
+// textured kernels never evaluate alpha_cut for a candidate.
+// Scratch-free like k_lit_build: trav_step's stack lives in LDS, kOccStack entries per lane.  Its
+// spill (stack_spill) moves kOccStack / 2 entries at a time and gives up when they do not fit in
+// kSpillDepth: kOccStack / 2 > kSpillDepth, so the spill array is never written or read (it points at
+// one LDS word), and 3 * depth <= 71 < kOccStack - 3 (pt_create) never gets that far anyway.
+constexpr int kOccStack = 2 * kSpillDepth + 2;
+static_assert(kOccStack / 2 > kSpillDepth && kOccStack - 3 > 72, "k_occ_build: the spill must stay unused");
+
+__global__ __launch_bounds__(kLitBlock) void k_occ_build(DevScene S, const uint32_t* __restrict__ tri_words,
+                                                        uint32_t cells, uint32_t words, const DevLight* __restrict__ lights,
+                                                        int n_lights, const uint32_t* __restrict__ bits,
+                                                        int* __restrict__ occ) {
+    __shared__ int lds_stack[kOccStack * kLitBlock];
+    __shared__ int lds_spill[1];
+    const uint64_t id = (uint64_t)blockIdx.x * kLitBlock + threadIdx.x;
+    if (id >= (uint64_t)cells * (uint64_t)n_lights) return;
+    const int li = (int)(id / cells);
+    const uint32_t cell = (uint32_t)(id - (uint64_t)li * cells);
+    int cand = -1;
+    do {
+        if ((bits[(size_t)li * words + (cell >> 5)] >> (cell & 31)) & 1u) break;  // lit: no shadow ray here
+        int a = 0, b = S.ntri - 1;  // the triangle of the cell, as k_lit_build
+        while (a < b) {
+            const int m = (a + b + 1) >> 1;
+            if (lit_first(tri_words[m]) <= cell) a = m; else b = m - 1;
+        }
+        const int t = a;
+        const uint32_t w = tri_words[t];
+        const int k = lit_level(w);
+        if (k == kLitNoCells || cell - lit_first(w) >= lit_cells(k)) break;
+        const DevLight lt = lights[li];
+        if (!(fabsf(lt.px) <= kLitMaxCoord && fabsf(lt.py) <= kLitMaxCoord && fabsf(lt.pz) <= kLitMaxCoord)) break;
+        const float4 A = S.isect[3 * t], E1 = S.isect[3 * t + 1], E2 = S.isect[3 * t + 2];
+        int cu[3], cv[3];
+        lit_cell_corners(k, cell - lit_first(w), cu, cv);
+        const float s = 1.0f / (3.0f * (float)(1 << k));
+        const float u = (float)(cu[0] + cu[1] + cu[2]) * s, v = (float)(cv[0] + cv[1] + cv[2]) * s;
+        const f3 e1 = mk(E1.x, E1.y, E1.z), e2 = mk(E2.x, E2.y, E2.z);
+        const f3 p = mk(A.x, A.y, A.z) + u * e1 + v * e2;
+        const f3 n = cross(e1, e2);
+        const float nl = length(n);
+        if (!(nl > 0.0f)) break;
+        f3 ng = n / nl;
+        const f3 ldir = mk(lt.px, lt.py, lt.pz) - p;
+        float h = dot(ldir, ng);
+        if (h < 0.0f) {
+            ng = -ng;
+            h = -h;
+        }
+        if (!(h > kLitDelta)) break;  // also NaN
+        TravState st;
+        TravStats ts;
+        trav_init(st, p + 1e-3f * ng, normalize(ldir), 0.0f, length(ldir));
+        while (!trav_step<kRayClosest, false, kOccStack, false>(S, st, lds_stack + threadIdx.x, kLitBlock, lds_spill, ts)) {
+        }
+        if (st.h.tri >= 0 && st.h.tri < S.ntri && __float_as_int(S.isect[3 * st.h.tri + 2].w) == 0) cand = st.h.tri;
+    } while (false);
+    occ[id] = cand;
+}
+
 }  // namespace
+
+// Rebuilds the occluder candidates of n_lights lights (cells entries each) on `stream`, after the
+// lit bits they skip (lit_build on the same stream).
+hipError_t occ_build(const DevScene& S, const uint32_t* tri_words, uint32_t cells, uint32_t words,
+                     const DevLight* lights, int n_lights, const uint32_t* bits, int* occ, hipStream_t stream) {
+    if (n_lights <= 0 || cells == 0) return hipSuccess;
+    const uint64_t n = (uint64_t)cells * (uint64_t)n_lights;
+    hipLaunchKernelGGL(k_occ_build, dim3((unsigned)((n + kLitBlock - 1) / kLitBlock)), dim3(kLitBlock), 0, stream, S,
+                       tri_words, cells, words, lights, n_lights, bits, occ);
+    return hipGetLastError();
+}
 
 // Clears and rebuilds the bits of n_lights lights (words 32-bit words each) on `stream`; diag: the
 // scene box's diagonal (lit_margin_cell).

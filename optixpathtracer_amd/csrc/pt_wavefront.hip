@@ -894,12 +894,32 @@ __device__ __forceinline__ void lit_count_wave(bool answered, int* lds) {
     const unsigned long long m = __ballot(answered ? 1 : 0);
     if (lane_id() == 0) lds[threadIdx.x >> 6] = __popcll(m);
 }
-template <int WAVES>
+template <int WAVES, int SLOT = 27>
 __device__ __forceinline__ void lit_count_block(const DevLaunch& L, const int* lds) {
     if (threadIdx.x != 0 || !L.counters) return;
     int tot = 0;
     for (int w = 0; w < WAVES; ++w) tot += lds[w];
-    if (tot > 0) atomicAdd(&L.counters[27], (unsigned long long)tot);
+    if (tot > 0) atomicAdd(&L.counters[SLOT], (unsigned long long)tot);
+}
+// The occluder candidate table (pt_lit.hip k_occ_build): `t` = the entry light * cells + cell of a
+// shadow ray the lit table left open (its origin is offset to the light's side of a triangle with
+// cells), -1 or a triangle.  True: the candidate passes the tracer's own test on this very ray -- tri_test with tmin 0 and the
+// ray's tmax, then tri_accept with inv and io formed as trav_init forms them -- so k_trace_pair /
+// k_shadow_vis would answer "occluded": they reach that triangle (every BVH box that holds it
+// contains its padded box) or stop earlier at another hit.  That holds for ANY entry, so a stale or
+// wrong one only costs the test.  A cut-out triangle (E2.w != 0, alpha_cut may drop its hits in the
+// textured kernels) never answers.  pt_stats.occluder_table_answers counts them (slot 28).
+constexpr int kOccCounter = 28;
+template <bool TEX>
+__device__ __forceinline__ bool occ_answers(const DevScene& S, int t, f3 o, f3 d, float tmax) {
+    if (t < 0) return false;
+    const float4 A = S.isect[3 * t], E1 = S.isect[3 * t + 1], E2 = S.isect[3 * t + 2];
+    float th, uh, vh;
+    bool bk;
+    if (!tri_test(A, E1, E2, o, d, 0.0f, tmax, th, uh, vh, bk)) return false;
+    if (TEX && __float_as_int(E2.w) != 0) return false;
+    const f3 inv = safe_inv(d);
+    return tri_accept(A, E1, E2, inv, mk(o.x * inv.x, o.y * inv.y, o.z * inv.z), th);
 }
 
 // Bounce-0 shadow dedup (with primary dedup): a pixel's first hit is the same in every frame
@@ -958,7 +978,12 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
     float4* nd = W.ray_d[(b + 1) & 1];
     __shared__ int lds_sh[kSortKeys * kWaves + kSortKeys + 1], lds_q[kSortKeys * kWaves + kSortKeys + 1];
     __shared__ int lds_lit[kWaves];
+    // the occluder candidates: Lambert only -- the register-bound Conductor and Dielectric kernels
+    // spill more with the code present even when the table is off
+    constexpr bool kOcc = MODE == kModeLambert;
+    __shared__ int lds_occ[kOcc ? kWaves : 1];
     const bool lit = !vis0 && L.lit_tri;  // the lit table answers this bounce's NEE tests where it can
+    const bool occ = kOcc && lit && L.occ_tab;
     if (blockIdx.x == 0 && threadIdx.x == 0 && L.counters) atomicAdd(&L.counters[15], (unsigned long long)n);
     if ((int)(blockIdx.x * kBlock) >= n) return;  // block-uniform
     {
@@ -971,6 +996,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
         float stmax = 0.0f;
         int path = 0;
         int shadow_light = 0;
+        int occ_t = -1;  // the shadow ray's entry of the occluder table: -1 or a triangle
         const int P1 = L.width * L.height;
         float4 l0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // shade0: the path's radiance after bounce 0
         if (valid) {
@@ -1032,6 +1058,8 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
                             stmax = length(ldir);
                             emit_shadow = true;
                             shadow_light = li;
+                            if (kOcc && occ && lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta)
+                                occ_t = L.occ_tab[li * (int)L.lit_cells + lit_c];  // lands while the BSDF is sampled
                         }
                     }
                 }
@@ -1054,9 +1082,25 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
             stqs(nd + qi, make_float4(d.x, d.y, d.z, 0.0f));
             if (kBetaQ) stqs(queue_beta(W, b + 1) + qi, make_float4(beta.x, beta.y, beta.z, __uint_as_float(seed)));
         }
+        if constexpr (kOcc) {
+            // here and not where the ray is built: with the surface still live the test cost 19 spilled
+            // VGPRs; one int (the entry, loaded there) carried across the extension-queue stores costs 2
+            // (DESIGN.md §5 v61).
+            // The origin is the one k_trace_pair will read: the continuation ray's where the record
+            // shares it (below), else so -- the same expression, and the same bits either way.
+            if (occ) {
+                bool answered = false;
+                if (occ_t >= 0) answered = occ_answers<TEX>(S, occ_t, (kShareOrigin && emit_next) ? o : so, sdir, stmax);
+                if (answered) emit_shadow = false;  // occluded: no ray, nothing to add
+                lit_count_wave(answered, lds_occ);
+            }
+        }
         const int si = PT_SORT_SHADOW ? block_append_sorted<kWaves, kSortKeys>(cnt(W, b, kShadowQ),
                                                                               emit_shadow ? (shadow_light & (kSortKeys - 1)) : -1, lds_sh)
                                       : block_append<kWaves>(cnt(W, b, kShadowQ), emit_shadow, lds_sh);
+        if constexpr (kOcc) {
+            if (occ) lit_count_block<kWaves, kOccCounter>(L, lds_occ);
+        }
         if (emit_shadow) {
             // Lambert: a sampled direction is never below the surface (lambert_sample forces z >= 0),
             // so the continuation ray starts at the shadow ray's origin (sf.pos + 1e-3 * Ng, the
@@ -1270,11 +1314,12 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
     const float4* rd = W.ray_d[b & 1];
     __shared__ int lds_sh[kWavesShA + 1];
     __shared__ int lds_nee[kNeeBuckets * (kWavesShA + 1)], lds_smp[kSmpBuckets * (kWavesShA + 1)];
-    __shared__ int lds_lit[kWavesShA];
+    __shared__ int lds_lit[kWavesShA], lds_occ[kWavesShA];
     const bool lit = !vis0 && L.lit_tri;  // as k_shade_fused
+    const bool occ = lit && L.occ_tab;    // the occluder candidates (occ_answers)
     if ((int)(blockIdx.x * kBlockShA) >= n) return;  // block-uniform
     const int i = (int)(blockIdx.x * kBlockShA + threadIdx.x);
-    bool emit = false, lit_answer = false;
+    bool emit = false, lit_answer = false, occ_answer = false;
     int nee_bucket = -1, smp_bucket = -1, code = 0;
     f3 so, sdir;
     float stmax = 0.0f;
@@ -1325,13 +1370,19 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
                     stmax = length(ldir);
                     code = i | (nb << kItemBits);
                     emit = true;
+                    // an occluded item gets neither a shadow ray nor a NEE-queue entry
+                    if (occ && lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta)
+                        occ_answer = occ_answers<TEX>(S, L.occ_tab[li * (int)L.lit_cells + lit_c], so, sdir, stmax);
+                    if (occ_answer) emit = false;
                 }
             }
         }
     }
     if (lit) lit_count_wave(lit_answer, lds_lit);
+    if (occ) lit_count_wave(occ_answer, lds_occ);
     const int si = block_append<kWavesShA>(cnt(W, b, kShadowQ), emit, lds_sh);
     if (lit) lit_count_block<kWavesShA>(L, lds_lit);
+    if (occ) lit_count_block<kWavesShA, kOccCounter>(L, lds_occ);
     if (emit) {
         W.sh_o[si] = make_float4(so.x, so.y, so.z, __int_as_float(code));
         W.sh_d[si] = make_float4(sdir.x, sdir.y, sdir.z, stmax);

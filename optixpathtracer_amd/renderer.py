@@ -303,6 +303,31 @@ class OptixRenderer:
                                              bits.nbytes), "pt_lit_table_download")
         return d, tri, bits
 
+    def set_occluder_table(self, enable: bool | None) -> None:
+        """pt_set_occluder_table: before a shadow ray is emitted, test the cell's occluder candidate
+        with the tracer's arithmetic and drop the ray on a hit; None = auto (the default), images
+        bit-identical.  Needs the lit table in use."""
+        check(self.lib.pt_set_occluder_table(self.h, -1 if enable is None else (1 if enable else 0)),
+              "pt_set_occluder_table")
+
+    def occluder_table(self):
+        """The occluder candidates for the current lights, (lights * cells,) int32 laid out
+        light * cells + cell: -1 or a leaf-order triangle (pt_occluder_table_download); None while the
+        table is not in use."""
+        n = C.c_int64(0)
+        check(self.lib.pt_occluder_table_download(self.h, C.byref(n), None, 0), "pt_occluder_table_download")
+        if n.value == 0:
+            return None
+        e = np.zeros(n.value, np.int32)
+        check(self.lib.pt_occluder_table_download(self.h, C.byref(n), e.ctypes.data, e.nbytes), "pt_occluder_table_download")
+        return e
+
+    def upload_occluder_table(self, entries) -> None:
+        """pt_occluder_table_upload: replace the candidates until the next rebuild; every entry must be
+        -1 or a triangle index of the scene."""
+        e = np.ascontiguousarray(entries, np.int32)
+        check(self.lib.pt_occluder_table_upload(self.h, e.ctypes.data, e.nbytes), "pt_occluder_table_upload")
+
     def render_accumulate(self, spp: int, first_frame_id: int = 1) -> np.ndarray:
         """Clear, render frame ids first_frame_id .. +spp-1 and return the mean image
         (pt_render_accumulate); the sum stays in the device accumulator."""

@@ -3,7 +3,7 @@
     python tools/lit_table_probe.py counters sphere_box_diffuse sponza_class > profiles/lit_table_counters.jsonl
     python tools/lit_table_probe.py launch sphere_box_diffuse > profiles/lit_table_launch_loop.jsonl
 
-counters: per scene and table setting (off, on) at 1920x1080, depth 8, one 128-frame launch: a
+counters: per scene and table setting (off, lit table on, lit and occluder table on) at 1920x1080, depth 8, one 128-frame launch: a
   pass with per-kernel event timing and a pass with the traversal counters, as one JSON line.
   bvh_build_ms is each renderer's own pt_create; the first renderer of a process also pays the
   runtime's first-launch costs there, so later rows show the shorter, steady figure.
@@ -27,7 +27,8 @@ W, H, DEPTH = 1920, 1080, 8
 KEYS = ["segments", "shadow_rays", "pair_kernel_shadow_rays", "nee_unoccluded", "lit_table_answers", "lit_table_cells",
         "lit_table_bits_set", "lit_table_bytes", "lit_table_build_ms", "bvh_build_ms", "pair_kernel_ms",
         "pair_kernel_launches", "shade_kernel_ms", "shade_kernel_launches", "trace_kernel_ms", "trace_kernel_launches",
-        "total_render_ms", "triangles"]
+        "total_render_ms", "triangles", "occluder_table_answers", "occluder_table_candidates", "occluder_table_bytes",
+        "occluder_table_build_ms"]
 
 
 def has_table(r) -> bool:
@@ -37,20 +38,24 @@ def has_table(r) -> bool:
 def counters(names):
     for name in names:
         sc = scenes.make_scene(name)
-        for lit in (False, True):
+        for lit, occ in ((False, False), (True, False), (True, True)):
             r = setup_renderer(sc, W, H, DEPTH)
             r.set_lit_table(lit)
+            if hasattr(r.lib, "pt_set_occluder_table"):
+                r.set_occluder_table(occ)
+            elif occ:
+                continue
             r.accum_clear()
             r.render_frames(1, 128)  # warm-up (allocations)
             r.synchronize()
-            out = {"scene": name, "lit_table": lit}
+            out = {"scene": name, "lit_table": lit, "occluder_table": occ}
             for what in ("timing", "counts"):
                 r.stats_reset()
                 r.set_kernel_timing(what == "timing")
                 r.set_traversal_stats(what == "counts")
                 r.render_frames(129, 128)
                 st = r.stats()
-                out[what] = {k: st[k] for k in KEYS}
+                out[what] = {k: st[k] for k in KEYS if k in st}
             r.close()
             print(json.dumps(out), flush=True)
 
