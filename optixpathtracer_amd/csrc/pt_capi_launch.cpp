@@ -1,0 +1,433 @@
+// pt_capi_launch.cpp — enqueueing frames: the launch record, the queue budget, the wavefront plan and
+// its batches, the megakernel loop, the multi-device split.
+#include "pt_renderer.h"
+
+using namespace pt;
+
+namespace {
+
+int next_event_pair(pt_renderer* r, hipEvent_t* a, hipEvent_t* b) {
+    PT_HIP(r->timing.ev.next(a, b), "hipEventCreate");
+    return PT_OK;
+}
+
+DevLaunch make_launch(const pt_renderer* r, float* accum, uint32_t frame_base, uint32_t n_frames,
+                      double* accum64 = nullptr, size_t frame_stride = 0) {
+    DevLaunch L;
+    L.width = r->width;
+    L.height = r->height;
+    L.row0 = 0;
+    L.image_height = r->height;
+    std::memcpy(L.cam_pos, r->cam_pos, sizeof L.cam_pos);
+    std::memcpy(L.inv_view, r->inv_view, sizeof L.inv_view);
+    std::memcpy(L.inv_proj, r->inv_proj, sizeof L.inv_proj);
+    L.lights = r->d_lights;
+    L.n_lights = r->n_lights;
+    L.max_bounces = r->max_bounces;
+    L.frame_base = frame_base;
+    L.n_frames = n_frames;
+    L.accum = accum;
+    L.accum64 = accum64;
+    L.frame_stride = frame_stride;
+    L.counters = r->d_counters;
+    L.debug_pixel = r->d_debug ? r->debug_pixel : -1;
+    L.debug_frame = r->debug_frame;
+    L.debug = r->d_debug;
+    L.lit_tri = r->lit.active ? r->lit.d_tri.get() : nullptr;
+    L.lit_bits = r->lit.d_bits;
+    L.lit_words = r->lit.words;
+    L.occ_tab = r->lit.active && r->occ.active ? r->occ.d_tab.get() : nullptr;
+    L.lit_cells = r->lit.cells;
+    return L;
+}
+
+}  // namespace
+
+namespace pt {
+
+// Bytes the wavefront queues of all streams hold now.
+size_t queue_bytes_held(const pt_renderer* r) {
+    size_t b = r->wf.paths > 0 ? wavefront_bytes(r->wf.paths, r->wf.max_bounces) : 0;
+    for (int k = 1; k < pt_renderer::kMaxWFStreams; ++k)
+        if (r->xwf[k].paths > 0) b += wavefront_bytes(r->xwf[k].paths, r->xwf[k].max_bounces);
+    return b;
+}
+
+// The most bytes all streams' queues may hold together (pt_set_queue_budget): the caller's
+// figure, or by default a quarter of the device memory -- 72 GB on an MI355X, above the 56 GB the
+// 128-frame 1080p batch takes on one stream, so the Lambert, Default and Layered modes keep it,
+// while two-stream Conductor / Dielectric calls take 82-frame batches.  SIZE_MAX:
+// no budget.
+size_t queue_budget_bytes(const pt_renderer* r) {
+    if (r->queue_budget < 0) return SIZE_MAX;
+    if (r->queue_budget > 0) return (size_t)r->queue_budget;
+    size_t total = 0;
+    if (hipDeviceTotalMem(&total, r->device) != hipSuccess || total == 0) {
+        (void)hipGetLastError();
+        return SIZE_MAX;
+    }
+    return total / 4;
+}
+
+}  // namespace pt
+
+namespace {
+
+constexpr int kMaxWFPaths = 1 << 28;  // 56 GB of queues at 208 B per path
+
+// What plan_wavefront decides for one wavefront call.
+struct WFPlan {
+    int nf_cap = 1;      // frames per batch
+    int ns = 1;          // streams the batches (or the two bands) alternate between
+    bool bands = false;  // a one-frame call whose rows may split into two bands
+};
+
+// Queues for the plan's ns streams, nf_cap frames each; an allocation that fails for lack of
+// memory shrinks the plan (smaller batches on the first stream, fewer streams beyond it).
+int reserve_queues(pt_renderer* r, WFPlan* plan, size_t budget) {
+    const int P = r->width * r->height;
+    const int maxb = std::max(1, r->max_bounces);
+    int& nf_cap = plan->nf_cap;
+    for (int k = 0; k < plan->ns; ++k) {
+        WFState& w = k ? r->xwf[k] : r->wf;
+        // queues larger than the budget's share (a lowered budget) are allocated again, smaller
+        // (a budget below one frame's queues still allows one frame: no reallocation per call)
+        const bool over = budget != SIZE_MAX && w.paths > P &&
+                          (size_t)plan->ns * wavefront_bytes(w.paths, w.max_bounces) > budget;
+        if (w.paths < P * nf_cap || w.max_bounces < r->max_bounces || over) {
+            for (int j = 0; j < pt_renderer::kMaxWFStreams; ++j)
+                if (r->wf_stream(j)) PT_HIP(hipStreamSynchronize(r->wf_stream(j)), "hipStreamSynchronize");
+            wavefront_free(w);
+            hipError_t ae = wavefront_alloc(w, P * nf_cap, maxb);
+            if (ae == hipErrorOutOfMemory && k == 0) {
+                // queues of the other streams (an earlier call's, or a mode with more
+                // streams) go first, then the full batch again
+                bool freed = false;
+                for (int j = 1; j < pt_renderer::kMaxWFStreams; ++j)
+                    if (r->xwf[j].paths > 0) {
+                        wavefront_free(r->xwf[j]);
+                        freed = true;
+                    }
+                if (freed) ae = wavefront_alloc(w, P * nf_cap, maxb);
+            }
+            // the first stream's queues: halve the batch until they fit (every batch size gives
+            // the same image), PT_ERR_NOMEM only when one frame does not; the size that fitted
+            // stays the cap until the memory would take the full batch (plan_wavefront),
+            // pt_set_frames_per_launch or pt_resize
+            while (ae == hipErrorOutOfMemory && k == 0 && nf_cap > 1) {
+                nf_cap = (nf_cap + 1) / 2;
+                r->nf_fit = nf_cap;
+                ae = wavefront_alloc(w, P * nf_cap, maxb);
+            }
+            // the extra streams only overlap batches: when their queues do not fit, render on
+            // the k streams that do (the image is the same, added in frame order either way)
+            if (ae == hipErrorOutOfMemory && k > 0) {
+                plan->ns = k;
+                break;
+            }
+            PT_HIP(ae, "wavefront_alloc");
+        }
+    }
+    return PT_OK;
+}
+
+// The shape of a wavefront call of n frames: frames per batch, streams, bands, and the queues to
+// hold them (reserve_queues).
+int plan_wavefront(pt_renderer* r, uint32_t n, WFPlan* plan) {
+    // Frames per wavefront launch chain: the queues hold nf frames' paths (208 B each), at most
+    // kMaxWFPaths of them.  Batching amortises launch gaps and the per-kernel SIMT tail:
+    // Lambert 1080p 545 / 648 / 664 Msamples/s at 1 / 8 / 16 frames.
+    const int P = r->width * r->height;
+    const int maxb = std::max(1, r->max_bounces);
+    const int nf_full = std::max(1, std::min({r->frames_per_launch, (int)std::min<uint32_t>(n, 1u << 20),
+                                              kMaxWFPaths / std::max(1, P)}));
+    // a batch size that fitted after an out-of-memory halving is kept until the free memory
+    // (plus what the queues hold now) would take the full batch again
+    if (r->nf_fit > 0 && r->nf_fit < nf_full) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            if (free_b + queue_bytes_held(r) >= wavefront_bytes(P * nf_full, maxb)) r->nf_fit = 0;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    int nf_cap = std::min(nf_full, r->nf_fit > 0 ? r->nf_fit : (1 << 30));
+    // two batches or more: alternate them between two streams with their own queues, so one
+    // batch's kernels run beside the other's (the memory-bound shading of one beside the
+    // VALU-bound tracing of the other, and each kernel's SIMT tail filled); k_accum still adds
+    // the batches in frame order (accum_wait / accum_done)
+    const int nbatch = (int)((n + (uint32_t)nf_cap - 1) / (uint32_t)nf_cap);
+    // One frame (pt_render / pt_display_add_frame without render-ahead, the path a viewer that
+    // moves the camera every frame gets): its rows split into two bands, one per stream, so
+    // each band's kernels fill the other's SIMT tails.  Every pixel's path depends only on its
+    // pixel and frame id, so the image is the same bit for bit.
+    const bool bands = n == 1 && r->band_split && r->height >= 16;  // both bands non-empty
+    // auto: a second stream pays where one batch's shading fills the other's trace tails
+    // (Conductor +0.6 %, Dielectric +4 % at 128 frames); Lambert, Default and Layered run as
+    // fast on one stream with half the queue memory
+    const bool two = r->material_mode == PT_MAT_CONDUCTOR || r->material_mode == PT_MAT_DIELECTRIC;
+    const int want = r->wf_streams > 0 ? r->wf_streams : (bands || two ? 2 : 1);
+    const int ns = std::max(1, std::min(want, bands ? 2 : nbatch));
+    // the queue budget (pt_set_queue_budget): the ns streams' queues
+    // together stay within it, by smaller batches (every batch size gives the same image);
+    // queues that streams beyond ns still hold are freed when they would overrun it
+    const size_t budget = queue_budget_bytes(r);
+    if (budget != SIZE_MAX) {
+        const size_t per_frame = wavefront_bytes(P, maxb);
+        const int nf_b = (int)std::max<size_t>(1, budget / ((size_t)ns * per_frame));
+        nf_cap = std::min(nf_cap, nf_b);
+        size_t used = (size_t)ns * wavefront_bytes(P * nf_cap, maxb);
+        for (int k = ns; k < pt_renderer::kMaxWFStreams; ++k) {
+            if (r->xwf[k].paths == 0) continue;
+            const size_t held = wavefront_bytes(r->xwf[k].paths, r->xwf[k].max_bounces);
+            if (used + held <= budget) {
+                used += held;
+                continue;
+            }
+            PT_HIP(hipStreamSynchronize(r->xstream[k]), "hipStreamSynchronize");
+            wavefront_free(r->xwf[k]);
+        }
+    }
+    plan->nf_cap = nf_cap;
+    plan->ns = ns;
+    plan->bands = bands;
+    const int rc = reserve_queues(r, plan, budget);
+    if (rc != PT_OK) return rc;
+    r->last_streams = plan->ns;
+    r->last_batch = plan->nf_cap;
+    return PT_OK;
+}
+
+// The events a call on ns streams (nband row bands) needs besides its launches' pairs, and the
+// extra streams themselves.
+int fork_resources(pt_renderer* r, int ns, int nband) {
+    if (ns > 1) {
+        PT_HIP(r->ev_fork.ensure(hipEventDisableTiming), "hipEventCreate");
+        for (Event& e : r->ev_accum) PT_HIP(e.ensure(hipEventDisableTiming), "hipEventCreate");
+    }
+    for (int k = 1; k < ns; ++k)
+        if (!r->xstream[k]) {
+            PT_HIP(r->xstream[k].create(), "hipStreamCreate");
+            PT_HIP(r->ev_join[k].ensure(hipEventDisableTiming), "hipEventCreate");
+        }
+    if (nband > 1) PT_HIP(r->ev_band0.ensure(hipEventDisableTiming), "hipEventCreate");
+    return PT_OK;
+}
+
+// pt_set_kernel_timing: the event pairs of one batch's trace and shading launches (null without).
+int timing_events(pt_renderer* r, bool fused, const hipEvent_t** tev, const hipEvent_t** sev) {
+    pt_renderer::Timing& t = r->timing;
+    *tev = *sev = nullptr;
+    if (!t.kernel_timing) return PT_OK;
+    t.tev_frame.resize(2 * (size_t)(r->max_bounces + 1));  // <= max_bounces + 1 trace launches
+    // launch 0 is the batch's k_extend; in the fused modes the others are k_trace_pair
+    for (int k = 0; k <= r->max_bounces; ++k)
+        PT_HIP((k > 0 && fused ? t.pev : t.tev).next(&t.tev_frame[2 * k], &t.tev_frame[2 * k + 1]), "hipEventCreate");
+    *tev = t.tev_frame.data();
+    t.sev_frame.resize(2 * (size_t)(r->max_bounces + 1));  // <= max_bounces shading launches
+    for (int k = 0; k <= r->max_bounces; ++k)
+        PT_HIP(t.sev.next(&t.sev_frame[2 * k], &t.sev_frame[2 * k + 1]), "hipEventCreate");
+    *sev = t.sev_frame.data();
+    return PT_OK;
+}
+
+// The queues of stream sk for one batch; a speculative batch also carries the cancel words.
+WFState batch_queues(pt_renderer* r, int sk, bool speculative, bool first_batch) {
+    WFState wq = sk ? r->xwf[sk] : r->wf;
+    if (speculative && r->ahead.d_cancel_seen) {  // a look-ahead batch: its kernels poll the cancel words
+        wq.cancel_host = r->ahead.cancel.d;
+        wq.cancel_seen = r->ahead.d_cancel_seen;
+        wq.cancel_epoch = r->ahead.cancel_epoch;
+        if (r->ahead.debug_hold && r->ahead.hold.d && first_batch) {  // pt_set_debug_hold: k_hold first
+            wq.hold_release = r->ahead.hold.d;
+            r->ahead.held++;
+        }
+    }
+    return wq;
+}
+
+// Enqueue the n frames of a wavefront call in the plan's batches, with their events, bands and
+// cancel words.
+int enqueue_wavefront(pt_renderer* r, const WFPlan& plan, float* accum, uint32_t first, uint32_t n, double* accum64,
+                      size_t frame_stride, bool speculative) {
+    int rc = PT_OK;
+    const DevScene S = r->scene();
+    // Lambert / Conductor / Dielectric: k_extend at bounce 0, then k_trace_pair per bounce
+    const bool fused = r->material_mode == PT_MAT_LAMBERT || r->material_mode == PT_MAT_CONDUCTOR ||
+                       r->material_mode == PT_MAT_DIELECTRIC;
+    const int ns = plan.ns, nf_cap = plan.nf_cap;
+    const bool dual = ns > 1;
+    const int nband = plan.bands && ns > 1 ? 2 : 1;  // row bands of a one-frame call
+    if ((rc = fork_resources(r, ns, nband)) != PT_OK) return rc;
+    int dev_cus = 256;
+    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, r->device);
+    if ((rc = lit_prepare(r)) != PT_OK) return rc;  // before the fork: every stream sees the new bits
+    hipEvent_t a = nullptr, b = nullptr;  // dual: one event pair around the whole call
+    if (dual) {
+        rc = next_event_pair(r, &a, &b);
+        if (rc) return rc;
+        PT_HIP(hipEventRecord(a, r->stream), "hipEventRecord");
+        PT_HIP(hipEventRecord(r->ev_fork, r->stream), "hipEventRecord");
+        for (int k = 1; k < ns; ++k) PT_HIP(hipStreamWaitEvent(r->xstream[k], r->ev_fork, 0), "hipStreamWaitEvent");
+    }
+    // band 0 is the smaller one (7/16 of the rows), so it finishes first and pt_render's
+    // download of its rows overlaps the rest of band 1
+    const int rows0 = r->height * 7 / 16;
+    r->band0_rows = nband > 1 ? rows0 : 0;
+    int batch = 0;
+    for (uint32_t f = 0; f < n; ++batch) {  // one event pair per batch (the batch's kernel chain)
+        const int nf = (int)std::min<uint32_t>((uint32_t)nf_cap, n - f);
+        DevLaunch L = make_launch(r, frame_stride ? accum + (size_t)f * frame_stride : accum, first + f,
+                                  (uint32_t)nf, accum64, frame_stride);
+        const int band = nband > 1 ? batch : 0;
+        if (nband > 1) {  // rows [row0, row0 + height) of the frame; the sum buffers at the band
+            L.row0 = band == 0 ? 0 : rows0;
+            L.height = band == 0 ? rows0 : r->height - rows0;
+            const size_t off = 3 * (size_t)r->width * (size_t)L.row0;
+            L.accum += off;
+            if (L.accum64) L.accum64 += off;
+        }
+        const int sk = batch % ns;  // stream of this batch
+        hipStream_t st = r->wf_stream(sk);
+        if (!dual) {
+            rc = next_event_pair(r, &a, &b);
+            if (rc) return rc;
+        }
+        const hipEvent_t* tev = nullptr;
+        const hipEvent_t* sev = nullptr;
+        if ((rc = timing_events(r, fused, &tev, &sev)) != PT_OK) return rc;
+        if (!dual) PT_HIP(hipEventRecord(a, r->stream), "hipEventRecord");
+        int n_timed = 0, n_stimed = 0;
+        const WFState wq = batch_queues(r, sk, speculative, batch == 0);
+        // batches add into the sum in frame order; bands touch disjoint pixels
+        const hipEvent_t accum_wait = dual && batch > 0 && nband == 1 ? r->ev_accum[(batch - 1) & 1].e : nullptr;
+        const hipEvent_t accum_done = dual && nband == 1 ? r->ev_accum[batch & 1].e : nullptr;
+        PT_HIP(launch_wavefront_frame(r->material_mode, r->trav_stats, S, L, wq, first + f,
+                                      nf, r->primary_dedup, dev_cus, st, tev, &n_timed,
+                                      accum_wait, accum_done, sev, &n_stimed, ns == 1 && r->wide_trace),
+               "wavefront launch");
+        if (tev) {  // pairs never recorded (the last ones handed out)
+            const int unused = r->max_bounces + 1 - n_timed;
+            const int unused_pair = fused ? std::min(unused, r->max_bounces) : 0;
+            r->timing.pev.give_back((size_t)unused_pair);
+            r->timing.tev.give_back((size_t)(unused - unused_pair));
+        }
+        if (sev) r->timing.sev.give_back((size_t)(r->max_bounces + 1 - n_stimed));
+        if (!dual) PT_HIP(hipEventRecord(b, r->stream), "hipEventRecord");
+        if (nband > 1 && band == 0) PT_HIP(hipEventRecord(r->ev_band0, st), "hipEventRecord");
+        if (band + 1 == nband) f += (uint32_t)nf;
+    }
+    if (dual) {
+        for (int k = 1; k < ns; ++k) {
+            PT_HIP(hipEventRecord(r->ev_join[k], r->xstream[k]), "hipEventRecord");
+            PT_HIP(hipStreamWaitEvent(r->stream, r->ev_join[k], 0), "hipStreamWaitEvent");
+        }
+        PT_HIP(hipEventRecord(b, r->stream), "hipEventRecord");
+    }
+    return PT_OK;
+}
+
+// The megakernel: chunks of frames_per_launch frames on the library stream, one event pair each.
+int enqueue_megakernel(pt_renderer* r, int kernel, float* accum, uint32_t first, uint32_t n) {
+    const DevScene S = r->scene();
+    const uint32_t chunk = (uint32_t)std::max(1, r->frames_per_launch);
+    for (uint32_t done = 0; done < n;) {
+        uint32_t k = std::min(chunk, n - done);
+        DevLaunch L = make_launch(r, accum, first + done, k);
+        hipEvent_t a, b;
+        const int rc = next_event_pair(r, &a, &b);
+        if (rc) return rc;
+        PT_HIP(hipEventRecord(a, r->stream), "hipEventRecord");
+        PT_HIP(launch_render(kernel, r->material_mode, r->trav_stats, S, L, r->stream), "render launch");
+        PT_HIP(hipEventRecord(b, r->stream), "hipEventRecord");
+        done += k;
+    }
+    return PT_OK;
+}
+
+}  // namespace
+
+namespace pt {
+
+// Launch frames [first, first+n) in chunks, adding into accum; brackets with events.  Does not
+// wait for earlier work: the event pairs of every launch since the last synchronisation point
+// are summed at the next pt_synchronize / pt_get_stats / download (collect_pending).
+// frame_stride > 0 (wavefront only): frame first + j is written alone to accum + j * frame_stride.
+int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, double* accum64, size_t frame_stride,
+                  bool speculative) {
+    int rc = PT_OK;
+    // callers that never synchronise through the library (pt_stream interop, device sum buffers,
+    // loops over pt_launch / pt_display_add_frame) would grow the event pools without bound:
+    // past kMaxPendingEvents pairs, retire them first (this waits for the enqueued work)
+    const pt_renderer::Timing& t = r->timing;
+    if (t.ev.used + t.tev.used + t.pev.used + t.sev.used > kMaxPendingEvents && (rc = collect_pending(r)) != PT_OK)
+        return rc;
+    r->timing.pending = true;
+    r->band0_rows = 0;  // set by enqueue_wavefront when this call renders its frame in row bands
+    r->lit.active = false;  // the wavefront branch decides (lit_prepare)
+    // AUTO = wavefront: it beats the megakernel in every material mode (1080p
+    // depth 8, 16 frames per launch, Msamples/s wavefront / megakernel: Lambert 725 / 414,
+    // Dielectric 1239 / 758, Default 255 / 104).
+    int kernel = r->kernel;
+    if (kernel == PT_KERNEL_AUTO) kernel = PT_KERNEL_WAVEFRONT;
+    if (accum64 && kernel != PT_KERNEL_WAVEFRONT)
+        return fail(PT_ERR_INVALID, "fp64 accumulation (pt_set_accum_fp64) runs with the wavefront kernel");
+    if (frame_stride && kernel != PT_KERNEL_WAVEFRONT)
+        return fail(PT_ERR_INVALID, "per-frame images (render-ahead) run with the wavefront kernel");
+    if (kernel == PT_KERNEL_WAVEFRONT) {
+        WFPlan plan;
+        if ((rc = plan_wavefront(r, n, &plan)) != PT_OK) return rc;
+        rc = enqueue_wavefront(r, plan, accum, first, n, accum64, frame_stride, speculative);
+    } else {
+        rc = enqueue_megakernel(r, kernel, accum, first, n);
+    }
+    if (rc != PT_OK) return rc;
+    r->timing.samples += (uint64_t)n * (uint64_t)r->width * (uint64_t)r->height;
+    r->timing.calls++;
+    return PT_OK;
+}
+
+// Multi-device pt_render_frames: frame ids first .. first+n-1 split into contiguous blocks
+// (device g renders first + g*n/N .. , the same split as optixpathtracer_amd/sharding.py), each
+// device adding its block in frame order into its own fp32 sum; then one ncclReduce (sum) of
+// the N sums onto device 0's accum().  Every sample keeps its (pixel, frame id) seed, so the
+// image equals the single-device one up to the fp32 order of the N-way sum.  Each device's work
+// and its reduce are enqueued on that device's stream; nothing waits here.
+int render_frames_multi(pt_renderer* r, uint32_t first, uint32_t n) {
+    const int N = (int)r->multi.comms.size();
+    const size_t count = 3 * (size_t)r->width * (size_t)r->height;
+    uint32_t f = first;
+    for (int g = 0; g < N; ++g) {
+        const uint32_t per = n / (uint32_t)N, extra = n % (uint32_t)N;
+        const uint32_t ng = per + ((uint32_t)g < extra ? 1u : 0u);
+        pt_renderer* d = g == 0 ? r : r->multi.peers[(size_t)g - 1];
+        if (ng > 0) {
+            PT_HIP(hipSetDevice(d->device), "hipSetDevice");
+            const int rc = launch_frames(d, g == 0 ? r->multi.d_part : d->accum(), f, ng,
+                                         r->accum64 ? (g == 0 ? r->multi.d_part64 : d->d_accum64) : nullptr);
+            if (rc) return rc;
+        }
+        f += ng;
+    }
+    ncclResult_t nr = ncclGroupStart();
+    for (int g = 0; g < N && nr == ncclSuccess; ++g) {
+        pt_renderer* d = g == 0 ? r : r->multi.peers[(size_t)g - 1];
+        if (r->accum64) {  // fp64 partial sums -> fp64 total on device 0
+            const double* send = g == 0 ? r->multi.d_part64 : d->d_accum64;
+            double* recv = g == 0 ? r->d_accum64 : d->d_accum64;  // significant on the root only
+            nr = ncclReduce(send, recv, count, ncclFloat64, ncclSum, 0, r->multi.comms[(size_t)g], d->stream);
+        } else {
+            const float* send = g == 0 ? r->multi.d_part : d->accum();
+            float* recv = g == 0 ? r->accum() : d->accum();  // significant on the root only
+            nr = ncclReduce(send, recv, count, ncclFloat32, ncclSum, 0, r->multi.comms[(size_t)g], d->stream);
+        }
+    }
+    const ncclResult_t ne = ncclGroupEnd();
+    (void)hipSetDevice(r->device);
+    if (nr != ncclSuccess || ne != ncclSuccess)
+        return fail(PT_ERR_HIP, std::string("ncclReduce: ") + ncclGetErrorString(nr != ncclSuccess ? nr : ne));
+    if (r->accum64) PT_HIP(accum_f64_to_f32(r->d_accum64, r->accum(), count, r->stream), "fp64 -> fp32 sum");
+    return PT_OK;
+}
+
+}  // namespace pt

@@ -1,5 +1,5 @@
-// pt_internal.h — host-side declarations shared by the C-ABI (pt_capi.cpp) and the kernel
-// translation units (pt_build.hip, pt_render.hip).  Not part of the public ABI.
+// pt_internal.h — host-side declarations shared by the C-ABI driver (pt_capi*.cpp, pt_renderer.h) and
+// the kernel translation units (pt_build.hip, pt_render.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -89,7 +89,7 @@ struct WFState {
     int* count = nullptr;                   // per bounce: queue, shadow, NEE and sample bucket lengths
     int paths = 0;
     int max_bounces = 0;
-    // Look-ahead cancellation (pt_capi.cpp cancel_look_ahead), set per batch: a speculative
+    // Look-ahead cancellation (pt_capi_ahead.cpp cancel_look_ahead), set per batch: a speculative
     // render-ahead batch carries the renderer's cancel words and the epoch it was enqueued under,
     // and its kernels stop early once the host has published a newer epoch (wf_cancelled,
     // trace_range).  Null for every other batch: no polling.

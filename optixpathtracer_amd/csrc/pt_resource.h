@@ -1,0 +1,150 @@
+// pt_resource.h — owners of the HIP resources the C-ABI driver (pt_capi*.cpp) holds: each releases
+// what it holds in its destructor, none can be copied.  Not part of the public ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+namespace pt {
+
+// n elements of device memory (hipMalloc / hipFree).  hipFree waits for the work that may still
+// read the memory.
+template <class T>
+class DevBuf {
+    T* p_ = nullptr;
+    size_t n_ = 0;
+
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    // Frees what it held first, so that memory is available to the new allocation.  On failure it
+    // is left empty, and a later launch's hipGetLastError does not see the failure.
+    hipError_t alloc(size_t n) {
+        reset();
+        const hipError_t e = hipMalloc((void**)&p_, sizeof(T) * n);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            p_ = nullptr;
+            return e;
+        }
+        n_ = n;
+        return hipSuccess;
+    }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t size() const { return n_; }
+    void swap(DevBuf& o) noexcept {
+        std::swap(p_, o.p_);
+        std::swap(n_, o.n_);
+    }
+};
+
+// One word of pinned host memory that kernels read over PCIe: `h` on the host, `d` the same word's
+// device address.
+struct PinnedWord {
+    unsigned* h = nullptr;
+    unsigned* d = nullptr;
+    PinnedWord() = default;
+    PinnedWord(const PinnedWord&) = delete;
+    PinnedWord& operator=(const PinnedWord&) = delete;
+    ~PinnedWord() { reset(); }
+    hipError_t alloc(unsigned init) {  // the host word alone; map() completes it
+        reset();
+        const hipError_t e = hipHostMalloc((void**)&h, sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent);
+        if (e != hipSuccess) {
+            h = nullptr;
+            return e;
+        }
+        *h = init;
+        return hipSuccess;
+    }
+    hipError_t map() {  // on failure the word is released
+        void* p = nullptr;
+        const hipError_t e = hipHostGetDevicePointer(&p, h, 0);
+        if (e != hipSuccess) reset();
+        else d = static_cast<unsigned*>(p);
+        return e;
+    }
+    void reset() {
+        if (h) (void)hipHostFree(h);
+        h = d = nullptr;
+    }
+};
+
+// A HIP event, created at its first use.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t ensure(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+
+// A non-blocking HIP stream.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+
+// Reusable HIP event pairs, one pair per timed launch; summed once the launches retire.
+struct EventPool {
+    std::vector<hipEvent_t> start, stop;
+    size_t used = 0;
+    EventPool() = default;
+    EventPool(const EventPool&) = delete;
+    EventPool& operator=(const EventPool&) = delete;
+    ~EventPool() {
+        for (hipEvent_t e : start) (void)hipEventDestroy(e);
+        for (hipEvent_t e : stop) (void)hipEventDestroy(e);
+    }
+    hipError_t next(hipEvent_t* a, hipEvent_t* b) {
+        if (used == start.size()) {
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            hipError_t e = hipEventCreate(&e0);
+            if (e == hipSuccess) e = hipEventCreate(&e1);
+            if (e != hipSuccess) return e;
+            start.push_back(e0);
+            stop.push_back(e1);
+        }
+        *a = start[used];
+        *b = stop[used];
+        used++;
+        return hipSuccess;
+    }
+    void give_back(size_t k) { used -= std::min(k, used); }  // the last k pairs went unrecorded
+    hipError_t collect(double* ms_sum, size_t* n) {
+        *ms_sum = 0.0;
+        *n = used;
+        if (used == 0) return hipSuccess;
+        hipError_t e = hipEventSynchronize(stop[used - 1]);
+        for (size_t i = 0; i < used && e == hipSuccess; ++i) {
+            float ms = 0.0f;
+            e = hipEventElapsedTime(&ms, start[i], stop[i]);
+            *ms_sum += ms;
+        }
+        used = 0;
+        return e;
+    }
+};
+
+}  // namespace pt

@@ -16,7 +16,7 @@ CSRC = Path(__file__).resolve().parent / "csrc"
 def kernel_sources_sha(csrc: Path = CSRC) -> str:
     """sha256 (first 16 hex digits) over the HIP sources, their headers and the launch code."""
     h = hashlib.sha256()
-    files = sorted(p for p in csrc.iterdir() if p.suffix in (".hip", ".h") or p.name == "pt_capi.cpp")
+    files = sorted(p for p in csrc.iterdir() if p.suffix in (".hip", ".h") or p.match("pt_capi*.cpp"))
     for p in files:
         h.update(p.name.encode())
         h.update(b"\0")

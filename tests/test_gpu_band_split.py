@@ -1,4 +1,4 @@
-"""One-frame calls in two row bands (pt_set_band_split, pt_capi.cpp launch_frames): a call that
+"""One-frame calls in two row bands (pt_set_band_split, pt_capi_launch.cpp launch_frames): a call that
 renders a single frame -- pt_render without render-ahead (the reference's one-Render-per-frame
 viewer with a camera that moves every frame, OptixView.cpp:201-210), pt_launch, pt_render_frames
 of one frame -- splits the frame's rows into two bands on the two wavefront streams.  A pixel's

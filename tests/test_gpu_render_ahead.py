@@ -1,4 +1,4 @@
-"""Render-ahead of pt_render / pt_display_add_frame (pt_set_render_ahead, pt_capi.cpp
+"""Render-ahead of pt_render / pt_display_add_frame (pt_set_render_ahead, pt_capi_ahead.cpp
 render_frame_image): the reference's viewer renders one sample per Render() call
 (OptixView::DrawOptix -> OptixRenderer::Render, OptixView.cpp:201-210, OptixRenderer.cpp:617-647).
 With render-ahead the library renders the following frame ids in one wavefront batch while the
@@ -199,7 +199,7 @@ def test_render_ahead_debug_pixel():
 @pytest.mark.parametrize("mode", [0, 1], ids=["default", "lambert"])
 def test_look_ahead_cancelled_by_camera_move(mode):
     """a camera move while the look-ahead batch is in
-    flight cancels it (pt_capi.cpp cancel_look_ahead; its kernels stop at their next poll,
+    flight cancels it (pt_capi_ahead.cpp cancel_look_ahead; its kernels stop at their next poll,
     pt_wavefront.hip wf_cancel_poll), and the next call's frame is the fresh render of the new
     camera, bit for bit.  With no time budget the ramp is 1, 2, ..., 64 frames, so call 64 is
     served from the first 64-frame slot and enqueues the next 64 frames on speculation.  The

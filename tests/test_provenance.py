@@ -36,6 +36,11 @@ def test_sources_sha_tracks_kernel_sources(tmp_path):
     h = copy / "pt_device.h"
     h.write_bytes(h.read_bytes() + b"\n")
     assert kernel_sources_sha(copy) != a
+    # the launch code is every pt_capi*.cpp: a byte appended to one of them changes the tag too
+    b = kernel_sources_sha(copy)
+    c = copy / "pt_capi_launch.cpp"
+    c.write_bytes(c.read_bytes() + b"\n")
+    assert kernel_sources_sha(copy) != b
 
 
 def test_pmc_record_only_current_sources(tmp_path):
