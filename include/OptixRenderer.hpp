@@ -176,6 +176,48 @@ class OptixRendererT {
     void CommitGeometry(bool rebuild = false) {
         check(pt_commit_geometry(r_, rebuild ? PT_GEOM_REBUILD : PT_GEOM_REFIT), "pt_commit_geometry");
     }
+    // --- beyond the reference: first-hit feature buffers and the a-trous denoiser (pt_aov_*, pt_denoise).
+    // One AOV (PT_AOV_*) of the present size, camera and geometry: W*H*channels floats, row 0 =
+    // bottom (PT_AOV_PRIM: the int32 indices' bits; AovPrim returns them as integers).
+    std::vector<float> Aov(int kind) {
+        const int ch = pt_aov_channels(kind);
+        if (ch < 0) throw std::runtime_error("Aov: no such kind");
+        std::vector<float> out((size_t)w_ * (size_t)h_ * (size_t)ch);
+        check(pt_aov_download(r_, kind, out.data(), (int64_t)(out.size() * sizeof(float))), "pt_aov_download");
+        return out;
+    }
+    std::vector<int32_t> AovPrim() {
+        std::vector<int32_t> out((size_t)w_ * (size_t)h_);
+        check(pt_aov_download(r_, PT_AOV_PRIM, out.data(), (int64_t)(out.size() * sizeof(int32_t))), "pt_aov_download");
+        return out;
+    }
+    static pt_denoise_options DenoiseDefaults() {
+        pt_denoise_options o;
+        o.struct_size = (uint32_t)sizeof o;
+        check(pt_denoise_options_default(&o), "pt_denoise_options_default");
+        return o;
+    }
+    // Filters the accumulated sum times `scale` (1 / spp: the mean) into h_pixels (W*H vec3).
+    template <class Vec3>
+    void Denoise(Vec3 h_pixels[], float scale, const pt_denoise_options* options = nullptr) {
+        static_assert(sizeof(Vec3) == 3 * sizeof(float), "h_pixels must be glm::vec3-like");
+        check(pt_denoise(r_, PT_DENOISE_SRC_ACCUM, nullptr, scale, options, reinterpret_cast<float*>(h_pixels)),
+              "pt_denoise");
+    }
+    // Filters a caller's image (W*H vec3) into h_pixels.
+    template <class Vec3>
+    void Denoise(const Vec3 source[], Vec3 h_pixels[], const pt_denoise_options* options = nullptr) {
+        static_assert(sizeof(Vec3) == 3 * sizeof(float), "h_pixels must be glm::vec3-like");
+        check(pt_denoise(r_, PT_DENOISE_SRC_HOST, reinterpret_cast<const float*>(source), 1.0f, options,
+                         reinterpret_cast<float*>(h_pixels)),
+              "pt_denoise");
+    }
+    pt_denoise_info DenoiseInfo() {
+        pt_denoise_info i;
+        i.struct_size = (uint32_t)sizeof i;
+        check(pt_get_denoise_info(r_, &i), "pt_get_denoise_info");
+        return i;
+    }
     pt_renderer* handle() { return r_; }
 
    private:

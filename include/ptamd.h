@@ -505,6 +505,68 @@ int pt_display_reset(pt_renderer* r, int32_t max_samples);
 int pt_display_add_frame(pt_renderer* r, int32_t* samples);
 int pt_display_download(pt_renderer* r, float* rgb);
 
+/* ---- first-hit feature buffers (AOVs) and the denoiser ----------------------
+ * The G-buffer: per pixel of the renderer's size, camera and committed geometry, the surface the
+ * pixel-centre camera ray hits first -- traced over the radiance ray's interval [0, 100] with its
+ * strict re-trace rule and alpha cut-out, reconstructed as the first bounce of a path is.  It does
+ * not depend on the frame id, the lights or the material mode.  Rows as the colour buffer (row 0 =
+ * bottom); a miss holds prim = -1 and 0 in every float.  It is rendered on first use and cached:
+ * only a new size, camera or geometry commit renders it again (pt_denoise_info.gbuffer_renders).
+ * Everything here runs on the library stream of device_list[0], so a call orders itself after the
+ * accumulation or display work already enqueued; it also waits behind a look-ahead batch in flight
+ * (pt_set_render_ahead). */
+#define PT_AOV_ALBEDO 0       /* float x 3: surface.albedo, after the textures */
+#define PT_AOV_NORMAL 1       /* float x 3: the shading normal (normal-mapped, face-forwarded) */
+#define PT_AOV_GEOM_NORMAL 2  /* float x 3: the geometric normal */
+#define PT_AOV_POSITION 3     /* float x 3 */
+#define PT_AOV_DEPTH 4        /* float x 1: the hit distance along the camera ray */
+#define PT_AOV_PRIM 5         /* int32 x 1: global triangle index, as pt_trace_rays reports it */
+#define PT_AOV_ROUGH_METAL 6  /* float x 2: roughness, metallic */
+/* Channels of one AOV (3, 3, 3, 3, 1, 1, 2); < 0 for a kind that does not exist. */
+int pt_aov_channels(int32_t kind);
+/* Renders the G-buffer if it is stale and copies one AOV to host; bytes must be W * H * channels * 4. */
+int pt_aov_download(pt_renderer* r, int32_t kind, void* host, int64_t bytes);
+/* The AOV on the device (W * H * channels elements); NULL until the G-buffer was first rendered.  It
+ * holds the view of the last render: pt_aov_download or pt_denoise bring it up to date. */
+const void* pt_aov_device_ptr(pt_renderer* r, int32_t kind);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the G-buffer's normal and
+ * position, on albedo-demodulated colour.  Every struct here leads with struct_size = the sizeof the
+ * caller compiled against: the library reads and writes min(struct_size, its own sizeof) bytes, and
+ * fields a shorter caller does not have take their defaults. */
+typedef struct pt_denoise_options {
+    uint32_t struct_size;
+    int32_t iterations;    /* 1..8; iteration i taps at a spacing of 2^i pixels */
+    int32_t demodulate;    /* != 0: filter colour / max(albedo, albedo_floor), multiply back afterwards */
+    float sigma_color;     /* halved per iteration */
+    float sigma_normal;
+    float sigma_position;
+    float albedo_floor;
+} pt_denoise_options;
+/* Fills the defaults (5, 1, 1.0, 0.3, 1.0, 1e-3) into the first o->struct_size bytes. */
+int pt_denoise_options_default(pt_denoise_options* o);
+#define PT_DENOISE_SRC_ACCUM 0   /* the sum buffer: with scale = 1/spp the values pt_accum_download gives */
+#define PT_DENOISE_SRC_DISPLAY 1 /* the pt_display_* buffer; PT_ERR_STATE before pt_display_reset */
+#define PT_DENOISE_SRC_HOST 2    /* host_in, W*H*3 floats */
+/* Filters source * scale (opt NULL = the defaults) into a device buffer of W*H*3 floats and, unless
+ * host_out is NULL, downloads it.  Miss pixels come back as they went in.  Asynchronous without
+ * host_out (except for the upload of a host source).  PT_ERR_INVALID for a bad source, iterations
+ * outside 1..8, or a sigma or floor that is not > 0; PT_ERR_STATE before the first pt_resize. */
+int pt_denoise(pt_renderer* r, int32_t source, const float* host_in, float scale, const pt_denoise_options* opt,
+               float* host_out);
+/* The last pt_denoise result on the device (W*H*3 floats); NULL before the first. */
+float* pt_denoised_device_ptr(pt_renderer* r);
+typedef struct pt_denoise_info {
+    uint32_t struct_size;
+    int32_t iterations;       /* of the last pt_denoise */
+    uint64_t gbuffer_renders; /* G-buffer renders since pt_create */
+    uint64_t hit_pixels;      /* pixels of the current G-buffer whose camera ray hits */
+    double gbuffer_ms;        /* HIP-event time of the last G-buffer render */
+    double filter_ms;         /* HIP-event time of the last pt_denoise's kernels (its G-buffer render excluded) */
+} pt_denoise_info;
+/* Waits for the library stream. */
+int pt_get_denoise_info(pt_renderer* r, pt_denoise_info* out);
+
 /* ---- glTF scene loading -----------------------------------------
  * ModelLoader::LoadModel (ModelLoading/ModelLoader.cpp:10-244): glTF 2.0 (.gltf with external
  * or data-URI buffers, or .glb) -> an owned pt_scene for pt_create.  One mesh per triangle

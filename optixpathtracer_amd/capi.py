@@ -167,6 +167,31 @@ class pt_lit_table_info(C.Structure):
                 ("words_per_light", C.c_uint32), ("delta", C.c_float), ("margin", C.c_float)]
 
 
+PT_AOV_ALBEDO, PT_AOV_NORMAL, PT_AOV_GEOM_NORMAL, PT_AOV_POSITION, PT_AOV_DEPTH, PT_AOV_PRIM, PT_AOV_ROUGH_METAL = range(7)
+PT_DENOISE_SRC_ACCUM, PT_DENOISE_SRC_DISPLAY, PT_DENOISE_SRC_HOST = range(3)
+
+AOV_KINDS = {
+    "albedo": PT_AOV_ALBEDO,
+    "normal": PT_AOV_NORMAL,
+    "geom_normal": PT_AOV_GEOM_NORMAL,
+    "position": PT_AOV_POSITION,
+    "depth": PT_AOV_DEPTH,
+    "prim": PT_AOV_PRIM,
+    "rough_metal": PT_AOV_ROUGH_METAL,
+}
+
+
+class pt_denoise_options(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("demodulate", C.c_int32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("albedo_floor", C.c_float)]
+
+
+class pt_denoise_info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("gbuffer_renders", C.c_uint64),
+                ("hit_pixels", C.c_uint64), ("gbuffer_ms", C.c_double), ("filter_ms", C.c_double)]
+
+
 class _pt_launch_frame(C.Structure):
     _fields_ = [("color_buffer", C.c_void_p), ("size", C.c_int32 * 2), ("id", C.c_uint32)]
 
@@ -249,6 +274,13 @@ SIGNATURES = {
     "pt_display_reset": (C.c_int, [_R, C.c_int32]),
     "pt_display_add_frame": (C.c_int, [_R, C.POINTER(C.c_int32)]),
     "pt_display_download": (C.c_int, [_R, _FP]),
+    "pt_aov_channels": (C.c_int, [C.c_int32]),
+    "pt_aov_download": (C.c_int, [_R, C.c_int32, C.c_void_p, C.c_int64]),
+    "pt_aov_device_ptr": (C.c_void_p, [_R, C.c_int32]),
+    "pt_denoise_options_default": (C.c_int, [C.POINTER(pt_denoise_options)]),
+    "pt_denoise": (C.c_int, [_R, C.c_int32, _FP, C.c_float, C.POINTER(pt_denoise_options), _FP]),
+    "pt_denoised_device_ptr": (C.c_void_p, [_R]),
+    "pt_get_denoise_info": (C.c_int, [_R, C.POINTER(pt_denoise_info)]),
     "pt_model_load_gltf": (C.c_int, [C.c_char_p, pt_image_decode_fn, C.c_void_p, C.POINTER(_M)]),
     "pt_model_scene": (C.POINTER(pt_scene), [_M]),
     "pt_model_mesh_name": (C.c_char_p, [_M, C.c_int32]),

@@ -197,6 +197,7 @@ int pt_resize(pt_renderer* r, int32_t width, int32_t height) {
     ring_free(r);
     r->d_accum.reset();
     r->d_display.reset();
+    r->aov.release();
     r->multi.d_part.reset();
     r->d_accum64.reset();
     r->multi.d_part64.reset();

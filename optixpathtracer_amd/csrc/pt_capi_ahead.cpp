@@ -26,6 +26,17 @@ static RenderKey render_key(const pt_renderer* r) {
     return k;
 }
 
+// The render key's share that a first hit depends on: size, camera and committed geometry.
+ViewKey view_key(const pt_renderer* r) {
+    const RenderKey k = render_key(r);
+    ViewKey v;
+    v.w = k.w;
+    v.h = k.h;
+    v.geom_version = k.geom_version;
+    std::memcpy(v.cam, k.cam, sizeof v.cam);
+    return v;
+}
+
 void ring_free(pt_renderer* r) {
     for (RingSlot& s : r->ahead.ring) {
         s.d.reset();  // hipFree waits for the work that may still read it

@@ -165,4 +165,36 @@ hipError_t sah_partial_launch(const BNode4* nodes, int n_nodes, double* partial,
 hipError_t display_fill(float* p, size_t n, float v, hipStream_t stream);
 hipError_t display_blend(float* fb, const float* frame, size_t n, float w, bool continuous, hipStream_t stream);
 
+// First-hit feature buffers and the a-trous filter (pt_aov.hip).  AovBuffers: what k_gbuffer writes
+// per pixel (row 0 = bottom): the seven AOVs of ptamd.h PT_AOV_*, the filter's 16-byte guide records
+// (normal | 1 at a hit, 0 at a miss; position | depth; albedo | 0) and the count of hit pixels.
+struct AovBuffers {
+    float *albedo, *normal, *gnormal, *position, *depth, *rough_metal;
+    int* prim;
+    float4 *guide_n, *guide_p, *guide_a;
+    unsigned long long* hits;  // one counter, zeroed by the caller
+};
+// L: width, height, row0, image_height and the camera are read, nothing else.
+hipError_t gbuffer_render(const DevScene& S, const DevLaunch& L, const AovBuffers& B, hipStream_t stream);
+// One filter iteration: cin -> cout, or with `last` -> out (W*H*3, remodulated).
+struct AtrousParams {
+    const float4* cin;
+    float4* cout;
+    float* out;
+    const float4 *gn, *gp, *ga;
+    int w, h, step;
+    float inv_c, inv_n, inv_p, floor;
+    int demodulate;
+};
+// The iterations of a step up to lds_max_step (at most kAtrousLdsMaxStep; 0 = none) stage their
+// tile and its halo in LDS, the others load every tap from global memory.  Same bits either way.
+// Steps 1, 2, 4: a (16 + 4 step)^2 tile of 48 B records (49 KB at step 4); steps 8 and 16: 12 rows
+// `step` apart of 32 + 4 step records (55 KB at step 16).
+constexpr int kAtrousLdsMaxStep = 16;
+constexpr int kAtrousLdsDefaultStep = 16;  // what pt_denoise uses: the fastest measured
+// c[p] = in[p] * scale, divided by max(albedo, floor) at the hit pixels when demodulate.
+hipError_t atrous_pack(const float* in, float scale, bool demodulate, float floor, const float4* gn, const float4* ga,
+                       float4* c, size_t n, hipStream_t stream);
+hipError_t atrous_iteration(const AtrousParams& A, bool last, int lds_max_step, hipStream_t stream);
+
 }  // namespace pt

@@ -1,6 +1,6 @@
 // pt_renderer.h — the renderer behind the C ABI (include/ptamd.h) and what the driver's translation
 // units share: pt_capi.cpp (entry points), pt_capi_bake.cpp, pt_capi_scene.cpp, pt_capi_launch.cpp,
-// pt_capi_ahead.cpp, pt_capi_tables.cpp and pt_capi_stats.cpp.  Not part of the public ABI.
+// pt_capi_ahead.cpp, pt_capi_tables.cpp, pt_capi_stats.cpp and pt_capi_denoise.cpp.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -100,6 +100,17 @@ struct RenderKey {
                debug_frame == o.debug_frame && debug_version == o.debug_version && geom_version == o.geom_version &&
                lights == o.lights &&
                std::memcmp(cam, o.cam, sizeof cam) == 0;
+    }
+};
+
+// What the first hit of a pixel depends on: the part of the render key that the G-buffer is cached
+// under (pt_capi_ahead.cpp view_key).
+struct ViewKey {
+    int w = 0, h = 0;
+    uint32_t geom_version = 0;
+    float cam[3 + 16 + 16] = {};
+    bool operator==(const ViewKey& o) const {
+        return w == o.w && h == o.h && geom_version == o.geom_version && std::memcmp(cam, o.cam, sizeof cam) == 0;
     }
 };
 
@@ -340,6 +351,33 @@ struct pt_renderer {
         pt::BuiltTable built;  // count: entries >= 0 of the last build or upload
     } occ;
 
+    // first-hit feature buffers and the denoiser (pt_capi_denoise.cpp, pt_aov.hip): the G-buffer of
+    // the view it was rendered for (gbuffer_prepare renders it again when view_key differs), the
+    // filter's ping-pong colour records, its W*H*3 result and the upload buffer of a host source.
+    // All of the renderer's size: pt_resize frees them.
+    struct Aov {
+        pt::DevBuf<float> d_albedo, d_normal, d_gnormal, d_position, d_depth, d_rough_metal;
+        pt::DevBuf<int> d_prim;
+        pt::DevBuf<float4> d_gn, d_gp, d_ga;  // guide records (pt_internal.h AovBuffers)
+        pt::DevBuf<unsigned long long> d_hits;
+        pt::DevBuf<float4> d_c[2];
+        pt::DevBuf<float> d_out, d_in;
+        pt::ViewKey key;
+        bool rendered = false;  // the G-buffer holds key's view
+        uint64_t renders = 0;
+        int iterations = 0;  // of the last pt_denoise
+        pt::Event ev_g[2], ev_f[2];  // around the last G-buffer render and the last filter run
+        bool g_timed = false, f_timed = false;
+        void release() {
+            for (pt::DevBuf<float>* b :
+                 {&d_albedo, &d_normal, &d_gnormal, &d_position, &d_depth, &d_rough_metal, &d_out, &d_in})
+                b->reset();
+            for (pt::DevBuf<float4>* b : {&d_gn, &d_gp, &d_ga, &d_c[0], &d_c[1]}) b->reset();
+            d_prim.reset();
+            rendered = g_timed = f_timed = false;
+        }
+    } aov;
+
     pt_renderer() = default;
     ~pt_renderer();  // the queue sets (wavefront_free); everything else releases itself
     pt::DevScene scene() const {
@@ -382,6 +420,7 @@ int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, doub
 int render_frames_multi(pt_renderer* r, uint32_t first, uint32_t n);
 
 // pt_capi_ahead.cpp
+ViewKey view_key(const pt_renderer* r);
 void ring_free(pt_renderer* r);
 void cancel_look_ahead(pt_renderer* r, bool force = false);
 int render_frame_image(pt_renderer* r, const float** img, hipEvent_t* ready = nullptr, bool look_ahead = false,
@@ -400,5 +439,8 @@ int occ_table_upload(pt_renderer* r, const int32_t* entries, int64_t bytes);
 
 // pt_capi_stats.cpp
 int collect_pending(pt_renderer* r);
+
+// pt_capi_denoise.cpp
+int gbuffer_prepare(pt_renderer* r);
 
 }  // namespace pt

@@ -268,6 +268,61 @@ class OptixRenderer:
         check(self.lib.pt_display_download(self.h, fptr(out)), "pt_display_download")
         return out
 
+    # -- first-hit feature buffers and the denoiser ----------------------------------------------
+    def aov(self, kind) -> np.ndarray:
+        """pt_aov_download: one first-hit feature buffer of the present size, camera and geometry,
+        by name (capi.AOV_KINDS) or PT_AOV_* value: (H, W, channels) float32, (H, W) for depth, and
+        (H, W) int32 for prim (-1 = miss).  Row 0 = bottom.  The G-buffer is rendered only when the
+        size, camera or committed geometry changed since the cached one."""
+        k = capi.AOV_KINDS[kind] if isinstance(kind, str) else int(kind)
+        ch = int(self.lib.pt_aov_channels(k))
+        if ch < 0:
+            raise capi.PTError(f"aov: no such kind {kind!r}", capi.PT_ERR_INVALID)
+        w, h = self.size
+        out = np.empty((h, w) if ch == 1 else (h, w, ch), np.int32 if k == capi.PT_AOV_PRIM else np.float32)
+        check(self.lib.pt_aov_download(self.h, k, out.ctypes.data, out.nbytes), "pt_aov_download")
+        return out
+
+    def denoise(self, source="accum", scale: float = 1.0, download: bool = True, **options):
+        """pt_denoise: the a-trous filter over source * scale, guided by the G-buffer.  source:
+        "accum" (the sum buffer; scale = 1 / spp gives the mean), "display" (the progressive view)
+        or an (H, W, 3) array.  options: fields of pt_denoise_options (iterations, demodulate,
+        sigma_color, sigma_normal, sigma_position, albedo_floor); the rest keep their defaults.
+        Returns the (H, W, 3) result; download=False leaves it on the device (pt_denoised_device_ptr,
+        asynchronous) and returns None."""
+        o = capi.pt_denoise_options()
+        o.struct_size = C.sizeof(o)
+        check(self.lib.pt_denoise_options_default(C.byref(o)), "pt_denoise_options_default")
+        for k, v in options.items():
+            if k == "struct_size" or k not in dict(capi.pt_denoise_options._fields_):
+                raise capi.PTError(f"denoise: no such option {k!r}", capi.PT_ERR_INVALID)
+            setattr(o, k, v)
+        w, h = self.size
+        host = None
+        if isinstance(source, str):
+            srcs = {"accum": capi.PT_DENOISE_SRC_ACCUM, "display": capi.PT_DENOISE_SRC_DISPLAY}
+            if source not in srcs:
+                raise capi.PTError(f"denoise: source must be 'accum', 'display' or an array, not {source!r}",
+                                   capi.PT_ERR_INVALID)
+            src = srcs[source]
+        else:
+            host = _f32(source)
+            if host.size != w * h * 3:
+                raise capi.PTError("denoise: the source array must hold H * W * 3 floats", capi.PT_ERR_INVALID)
+            src = capi.PT_DENOISE_SRC_HOST
+        out = np.empty((h, w, 3), np.float32) if download else None
+        check(self.lib.pt_denoise(self.h, src, fptr(host) if host is not None else None, float(scale), C.byref(o),
+                                  fptr(out) if download else None), "pt_denoise")
+        return out
+
+    def denoise_info(self) -> dict:
+        """pt_get_denoise_info: iterations and filter_ms of the last denoise(), gbuffer_renders since
+        the renderer was created, hit_pixels and gbuffer_ms of the G-buffer in force."""
+        s = capi.pt_denoise_info()
+        s.struct_size = C.sizeof(s)
+        check(self.lib.pt_get_denoise_info(self.h, C.byref(s)), "pt_get_denoise_info")
+        return {k: getattr(s, k) for k, _ in capi.pt_denoise_info._fields_ if k != "struct_size"}
+
     def accum_clear(self) -> None:
         check(self.lib.pt_accum_clear(self.h), "pt_accum_clear")
 

@@ -1,0 +1,138 @@
+"""What the first-hit G-buffer and the a-trous denoiser cost, beside one frame of path tracing.
+
+For the sphere box (about 35k triangles) and sponza_class (about 250k) at 1920x1080, a 4-spp sum is
+accumulated once and one JSON line per scene is printed (each figure the median of `--reps` calls
+after a warm-up call, with min and max):
+
+  gbuffer_ms            pt_denoise_info.gbuffer_ms (HIP events around k_gbuffer) of a call after a
+                        camera nudge, which makes the cached G-buffer stale
+  filter_ms             pt_denoise_info.filter_ms (HIP events around the pack pass and the iterations)
+                        at 1 .. `--iterations` iterations, for the plain global-load build of the
+                        iterations (plain) and with the iterations of a step up to 2 (lds2), 4
+                        (lds4) or 16 (lds16) staging their tile in LDS (PTAMD_DENOISE_LDS = 0, 2,
+                        4, 16), the variants alternating call by call
+  per_iteration_ms      differences of those medians: iteration i alone (iteration 0 with the pack pass)
+  floor_ms_per_iteration  64 B per pixel (48 B of colour and guide records read, 16 B written) at the
+                        6.29 TB/s a float4 copy reaches on this GPU
+  denoise_wall_ms       wall time of one pt_denoise from the accumulator at the defaults, left on
+                        the device (then pt_synchronize) and downloaded to the host
+  render_wall_ms        wall time of one one-frame pt_render in the same process, for scale
+
+No pass/fail bar.  The lines also go to `--out` (default profiles/denoise_bench.json).
+
+  python tools/denoise_bench.py [--reps 9] [--iterations 5] [--size 1920x1080] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+from optixpathtracer_amd import scenes  # noqa: E402
+from optixpathtracer_amd.renderer import setup_renderer  # noqa: E402
+
+COPY_TBS = 6.29  # measured float4 copy rate of the MI355X's HBM
+FLOOR_BYTES = 64  # per pixel and iteration: three 16-byte records read, one written
+
+
+def spread(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+
+
+def wall_ms(fn):
+    t0 = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def filter_ms(r, lds: int, iterations: int) -> float:
+    os.environ["PTAMD_DENOISE_LDS"] = str(lds)
+    r.denoise("accum", 0.25, download=False, iterations=iterations)
+    return r.denoise_info()["filter_ms"]
+
+
+def run(name, sc, w, h, depth, reps, iterations):
+    r = setup_renderer(sc, w, h, depth)
+    r.accum_clear()
+    r.render_frames(1, 4)
+    r.synchronize()
+    out = {"scene": name, "size": f"{w}x{h}", "triangles": r.stats()["triangles"], "reps": reps}
+
+    # the G-buffer: every call after a camera nudge renders it again
+    base = np.asarray(sc.camera_blender_pos, np.float32)
+    g = []
+    for k in range(reps + 1):
+        r.SetCameraBlender(base + np.float32([1e-3 * (k % 2), 0.0, 0.0]), sc.camera_blender_rot, sc.fov_deg)
+        r.denoise("accum", 0.25, download=False)
+        g.append(r.denoise_info()["gbuffer_ms"])
+    info = r.denoise_info()
+    assert info["gbuffer_renders"] == reps + 1
+    out["gbuffer_ms"] = spread(g[1:])
+    out["hit_pixels"] = info["hit_pixels"]
+
+    # the filter, plain against LDS-staged small steps (up to step 2, 4 or 16), alternating
+    variants = {"plain": 0, "lds2": 2, "lds4": 4, "lds16": 16}
+    ms = {v: {n: [] for n in range(1, iterations + 1)} for v in variants}
+    for n in range(1, iterations + 1):
+        for k in range(reps + 1):
+            for v, lds in variants.items():
+                t = filter_ms(r, lds, n)
+                if k:
+                    ms[v][n].append(t)
+    same = {}
+    for v, lds in variants.items():
+        os.environ["PTAMD_DENOISE_LDS"] = str(lds)
+        same[v] = r.denoise("accum", 0.25, iterations=iterations)
+    out["variants_identical"] = all(bool((same["plain"].view(np.uint32) == same[v].view(np.uint32)).all()) for v in variants)
+    floor = w * h * FLOOR_BYTES / (COPY_TBS * 1e12) * 1e3
+    out["floor_ms_per_iteration"] = floor
+    for v in variants:
+        med = [statistics.median(ms[v][n]) for n in range(1, iterations + 1)]
+        per = [med[0]] + [med[n] - med[n - 1] for n in range(1, iterations)]
+        out[f"filter_ms_{v}"] = {str(n): spread(ms[v][n]) for n in range(1, iterations + 1)}
+        out[f"per_iteration_ms_{v}"] = per
+    os.environ.pop("PTAMD_DENOISE_LDS", None)  # the library's default build from here on
+
+    dev, host = [], []
+    for k in range(reps + 1):
+        dev.append(wall_ms(lambda: (r.denoise("accum", 0.25, download=False), r.synchronize())))
+        host.append(wall_ms(lambda: r.denoise("accum", 0.25)))
+    out["denoise_wall_ms"] = {"device": spread(dev[1:]), "downloaded": spread(host[1:])}
+    out["filter_ms_default"] = r.denoise_info()["filter_ms"]
+
+    r.set_render_ahead(1)  # every call renders its own frame
+    img = np.empty((h, w, 3), np.float32)
+    rw = [wall_ms(lambda: r.Render(img)) for _ in range(reps + 1)]
+    out["render_wall_ms"] = spread(rw[1:])
+    r.close()
+    line = json.dumps(out)
+    print(line, flush=True)
+    return line
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--iterations", type=int, default=5)
+    ap.add_argument("--size", default="1920x1080")
+    ap.add_argument("--depth", type=int, default=8)
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "denoise_bench.json"))
+    a = ap.parse_args()
+    w, h = (int(x) for x in a.size.split("x"))
+    lines = [run("sphere_box_diffuse", scenes.sphere_in_box("diffuse"), w, h, a.depth, a.reps, a.iterations),
+             run("sponza_class", scenes.sponza_class(), w, h, a.depth, a.reps, a.iterations)]
+    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.out).write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
