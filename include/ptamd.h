@@ -249,8 +249,9 @@ int pt_set_frames_per_launch(pt_renderer* r, int32_t frames);
 /* Upper bound on the device memory of the wavefront queues of all streams together (VERDICT
    round 5 item 6; the reference holds a 25 MB colour buffer, OptixRenderer.cpp:649-660, so a
    drop-in sharing the GPU with a viewer should not take a third of it).  bytes > 0: that many;
-   0: the default, a quarter of the device memory (72 GB on an MI355X: the 128-frame 1080p batch
-   of one stream fits, two-stream Conductor / Dielectric calls take 82-frame batches); < 0: no
+   0: the default, a quarter of the device memory (hipDeviceTotalMem / 4: on an MI355X the
+   128-frame 1080p batch of one stream fits, two-stream Conductor / Dielectric calls take smaller
+   batches); < 0: no
    budget (only the 2^28-path cap per stream).  A call lowers its frames per batch to fit (every
    batch size gives the same image) and frees queues that streams it does not use hold beyond
    the budget; pt_stats.queue_bytes reports what the queues hold. */

@@ -626,11 +626,11 @@ int pt_get_trace_coherence(pt_renderer* r, uint64_t hist[8]) {
     PT_HIP(hipMemcpy(c, r->d_counters, sizeof c, hipMemcpyDeviceToHost), "download counters");
     uint64_t steps = 0;
     for (int k = 0; k < 6; ++k) {
-        hist[k] = c[20 + k];
-        steps += c[20 + k];
+        hist[k] = c[kCtrCoh0 + k];
+        steps += c[kCtrCoh0 + k];
     }
     hist[6] = steps;
-    hist[7] = c[26];
+    hist[7] = c[kCtrCohLanes];
     for (pt_renderer* p : r->multi.peers) {  // a multi-device renderer: every device's steps
         uint64_t ph[8];
         if ((rc = pt_get_trace_coherence(p, ph)) != PT_OK) return rc;

@@ -54,10 +54,10 @@ size_t queue_bytes_held(const pt_renderer* r) {
 }
 
 // The most bytes all streams' queues may hold together (pt_set_queue_budget): the caller's
-// figure, or by default a quarter of the device memory -- 72 GB on an MI355X, above the 56 GB the
-// 128-frame 1080p batch takes on one stream, so the Lambert, Default and Layered modes keep it,
-// while two-stream Conductor / Dielectric calls take 82-frame batches.  SIZE_MAX:
-// no budget.
+// figure, or by default a quarter of the device memory (hipDeviceTotalMem / 4) -- on an MI355X
+// above the 56 GB the 128-frame 1080p batch takes on one stream, so the Lambert, Default and
+// Layered modes keep it, while two-stream Conductor / Dielectric calls take smaller batches
+// (DESIGN.md §5).  SIZE_MAX: no budget.
 size_t queue_budget_bytes(const pt_renderer* r) {
     if (r->queue_budget < 0) return SIZE_MAX;
     if (r->queue_budget > 0) return (size_t)r->queue_budget;

@@ -96,7 +96,7 @@ int pt_get_stats(pt_renderer* r, pt_stats* out) {
     unsigned long long c[kCounters];
     PT_HIP(hipMemcpy(c, r->d_counters, sizeof c, hipMemcpyDeviceToHost), "download counters");
     std::memset(out, 0, sizeof *out);
-    out->segments = c[0];
+    out->segments = c[kCtrSegments];
     out->samples = r->timing.samples;
     out->last_render_ms = r->timing.last_ms;
     out->total_render_ms = r->timing.total_ms;
@@ -106,43 +106,43 @@ int pt_get_stats(pt_renderer* r, pt_stats* out) {
     out->bvh_build_ms = r->timing.bvh_ms;
     out->bvh_nodes = r->bvh_nodes;
     out->bvh_depth = r->bvh_depth;
-    out->nodes_visited = c[1];
-    out->tri_tests = c[2];
-    out->rays = c[3];
-    out->stack_overflows = c[4];
+    out->nodes_visited = c[kCtrNodes];
+    out->tri_tests = c[kCtrTriTests];
+    out->rays = c[kCtrRays];
+    out->stack_overflows = c[kCtrStackOverflows];
     out->triangles = r->ntri;
     out->trace_kernel_ms = r->timing.trace_ms;
     out->trace_kernel_launches = r->timing.trace_launches;
     out->pair_kernel_ms = r->timing.pair_ms;
     out->pair_kernel_launches = r->timing.pair_launches;
-    out->shadow_rays = c[5];
-    out->trace_kernel_rays = c[6];
-    out->trace_kernel_bytes = c[7];
-    out->strict_retraces = c[8];
-    out->wave_steps = c[9];
-    out->wave_active_lanes = c[10];
-    out->wave_node_steps = c[11];
-    out->wave_tri_steps = c[12];
-    out->wave_refills = c[13];
-    out->lds_nodes_visited = c[14];
+    out->shadow_rays = c[kCtrShadowRays];
+    out->trace_kernel_rays = c[kCtrTraceRays];
+    out->trace_kernel_bytes = c[kCtrTraceBytes];
+    out->strict_retraces = c[kCtrRetraces];
+    out->wave_steps = c[kCtrWaveSteps];
+    out->wave_active_lanes = c[kCtrWaveActive];
+    out->wave_node_steps = c[kCtrWaveNodeSteps];
+    out->wave_tri_steps = c[kCtrWaveTriSteps];
+    out->wave_refills = c[kCtrWaveRefills];
+    out->lds_nodes_visited = c[kCtrLdsNodes];
     out->shade_kernel_ms = r->timing.shade_ms;
     out->shade_kernel_launches = r->timing.shade_launches;
-    out->shade_kernel_items = c[15];
+    out->shade_kernel_items = c[kCtrShadeItems];
     out->frames_rendered_ahead = r->ahead.rendered;
     out->frames_served_ahead = r->ahead.served;
     out->look_ahead_cancelled = r->ahead.cancelled;
-    out->pair_kernel_rays = c[16];
-    out->pair_kernel_bytes = c[17];
-    out->pair_kernel_shadow_rays = c[19];
-    out->nee_unoccluded = c[18];
+    out->pair_kernel_rays = c[kCtrPairRays];
+    out->pair_kernel_bytes = c[kCtrPairBytes];
+    out->pair_kernel_shadow_rays = c[kCtrPairShadowRays];
+    out->nee_unoccluded = c[kCtrNeeUnoccluded];
     out->queue_bytes = queue_bytes_held(r);
     const size_t qb = queue_budget_bytes(r);
     out->queue_budget = qb == SIZE_MAX ? 0 : qb;
     out->last_streams = r->last_streams;
     out->last_batch_frames = r->last_batch;
     out->look_ahead_held = r->ahead.held;
-    out->lit_table_answers = c[27];
-    out->occluder_table_answers = c[28];
+    out->lit_table_answers = c[kCtrLitAnswers];
+    out->occluder_table_answers = c[kCtrOccAnswers];
     if ((rc = table_stats(r, out)) != PT_OK) return rc;
     out->geometry_commits = r->geom.commits;
     out->geometry_refits = r->geom.refits;

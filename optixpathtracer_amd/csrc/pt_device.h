@@ -87,7 +87,7 @@ struct DevLaunch {
     size_t frame_stride;             // 0: the frames add into accum; else frame f of the launch is
                                      // written alone to accum + f * frame_stride (pt_render's
                                      // render-ahead ring, wavefront k_accum only)
-    unsigned long long* counters;    // [0] segments [1] nodes visited [2] triangle tests [3] rays
+    unsigned long long* counters;    // kCounters slots (enum Counter below), NULL = not counted
     // debug path (pt_set_debug_pixel; the reference's isDebugRay, devicePrograms.cu:637-644):
     // the path of pixel debug_pixel (W*y + x, -1 = off) at frame debug_frame records every
     // bounce's surface into debug[bounce - 1] (kDebugRecordFloats floats each)
@@ -104,6 +104,36 @@ struct DevLaunch {
     const int* occ_tab;
     uint32_t lit_cells;
 };
+// Slots of DevLaunch::counters (pt_get_stats and pt_get_trace_coherence read them back).
+enum Counter : int {
+    kCtrSegments = 0,    // path segments
+    kCtrNodes,           // BVH nodes visited
+    kCtrTriTests,        // triangle tests
+    kCtrRays,            // rays traced
+    kCtrStackOverflows,  // traversal stack overflows
+    kCtrShadowRays,      // shadow rays
+    kCtrTraceRays,       // rays of the timed trace kernels (k_extend, k_trace_pair)
+    kCtrTraceBytes,      // their algorithmic queue bytes
+    kCtrRetraces,        // strict re-traces
+    // wave schedule of the trace kernels (pt_stats wave_*; shader cycles under PT_CYCLE_PROBE)
+    kCtrWaveSteps,
+    kCtrWaveActive,
+    kCtrWaveNodeSteps,
+    kCtrWaveTriSteps,
+    kCtrWaveRefills,
+    kCtrLdsNodes,         // node visits served from the top levels staged in LDS
+    kCtrShadeItems,       // items of the timed shading kernel (pt_stats shade_kernel_items)
+    kCtrPairRays,         // rays of the k_trace_pair launches alone (pt_stats pair_kernel_*)
+    kCtrPairBytes,        // their algorithmic queue bytes
+    kCtrNeeUnoccluded,    // k_trace_pair shadow rays that found their light unoccluded
+    kCtrPairShadowRays,   // shadow rays among kCtrPairRays
+    kCtrCoh0,             // trace coherence histogram (TravStats::coh): six buckets from here,
+    kCtrCohLanes = kCtrCoh0 + 6,  // then the lanes that loaded a global node
+    kCtrLitAnswers,       // NEE tests the lit table answered (pt_stats lit_table_answers)
+    kCtrOccAnswers,       // NEE tests the occluder candidate table answered
+    kCounters
+};
+static_assert(kCtrCoh0 == 20 && kCounters == 29, "the counter slots keep their numbers");
 constexpr int kDebugMaxBounces = 64;
 constexpr int kDebugRecordFloats = 22;  // ptamd.h pt_debug_bounce
 

@@ -84,8 +84,9 @@ struct WFState {
     float4* sh_c = nullptr;                 // deferred NEE contribution (fused modes)
     int* aux = nullptr;                     // light index << 1 | conductor (RNG-coupled modes)
     int* vis = nullptr;                     // shadow result per shadow ray (RNG-coupled modes)
-    int* nq = nullptr;                      // NEE items (RNG-coupled modes): kShadeBuckets regions of `paths`
-    int* sq = nullptr;                      // BSDF-sample items, same layout
+    int* nq = nullptr;                      // NEE items (RNG-coupled modes): kNeeRegions regions of `paths`,
+                                            // two buckets each, one from either end (pt_wavefront.hip)
+    int* sq = nullptr;                      // BSDF-sample items: kShadeBuckets regions of `paths`
     int* count = nullptr;                   // per bounce: queue, shadow, NEE and sample bucket lengths
     int paths = 0;
     int max_bounces = 0;
@@ -114,7 +115,7 @@ void wavefront_free(WFState& W);
 // primary_dedup: trace the batch's identical camera rays once per pixel (k_extend `dup`).
 // accum_wait / accum_done (optional): the batch's k_accum waits for accum_wait and records
 // accum_done, so batches on different streams still add into the sum in frame order.
-// wide_trace: the call runs on one stream, so the untextured trace kernels take the wide
+// wide_trace: the call runs on one stream, so the trace kernels take the wide
 // workgroups (pt_wavefront.hip kBlockTraceWide).
 hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const DevLaunch& L, const WFState& W,
                                   uint32_t frame, int nf, bool primary_dedup, int cus, hipStream_t stream,

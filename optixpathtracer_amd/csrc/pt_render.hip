@@ -39,14 +39,14 @@ __device__ __forceinline__ void flush_stats(const DevLaunch& L, uint32_t segs, c
         unsigned long long e = wave_sum((unsigned long long)ts.overflow);
         unsigned long long g = wave_sum((unsigned long long)ts.retrace);
         if (lane == 0 && L.counters) {
-            atomicAdd(&L.counters[1], b);
-            atomicAdd(&L.counters[2], c);
-            atomicAdd(&L.counters[3], d);
-            atomicAdd(&L.counters[4], e);
-            atomicAdd(&L.counters[8], g);
+            atomicAdd(&L.counters[kCtrNodes], b);
+            atomicAdd(&L.counters[kCtrTriTests], c);
+            atomicAdd(&L.counters[kCtrRays], d);
+            atomicAdd(&L.counters[kCtrStackOverflows], e);
+            atomicAdd(&L.counters[kCtrRetraces], g);
         }
     }
-    if (lane == 0 && L.counters) atomicAdd(&L.counters[0], a);
+    if (lane == 0 && L.counters) atomicAdd(&L.counters[kCtrSegments], a);
 }
 
 template <int MODE, bool STATS, bool TEX>

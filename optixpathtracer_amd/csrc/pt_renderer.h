@@ -33,12 +33,6 @@ int hip_fail(hipError_t e, const char* where);
         if (e__ != hipSuccess) return hip_fail(e__, where); \
     } while (0)
 
-// Device counters: [0] segments [1] nodes visited [2] triangle tests [3] rays [4] stack
-// overflows [5] shadow rays [6] timed trace-kernel rays [7] their bytes [8] strict re-traces
-// [9..13] wave schedule of the trace kernels (pt_stats wave_*) [14] node visits served from LDS
-// [15] items of the timed shading kernel (pt_stats shade_kernel_items) [16] [17] rays and
-// algorithmic bytes of the k_trace_pair launches alone (pt_stats pair_kernel_*).
-constexpr int kCounters = 29;  // [20..26]: trace coherence histogram (pt_get_trace_coherence)
 // event pairs held by one renderer before launch_frames retires them (EventPool)
 constexpr size_t kMaxPendingEvents = 4096;
 // the smallest traversal stack of any kernel (pt_device.h stack_capacity: 71 entries for the
@@ -208,7 +202,7 @@ struct pt_renderer {
     pt::DevBuf<unsigned long long> d_counters;
     bool primary_dedup = true;  // pt_set_primary_dedup
     bool band_split = true;     // pt_set_band_split: one-frame calls render two row bands on two streams
-    bool wide_trace = true;     // one-stream calls: wide trace workgroups (PT_WIDE_TRACE env 0 turns it off)
+    bool wide_trace = true;     // one-stream calls: wide trace workgroups (PTAMD_WIDE_TRACE env 0 turns it off)
     int frames_per_launch = 128;  // 56 GB of queues at 1080p (16 -> 64 frames +5 % Lambert,
                                   // 64 -> 128 with the ray pools +0.7 to +2.5 %)
     int nf_fit = 0;  // > 0: the largest batch whose queues fitted after an out-of-memory halving

@@ -77,19 +77,16 @@ constexpr int kBlockTraceWide = PT_TRACE_BLOCK_WIDE;
 template <int BLK>
 constexpr int lds_nodes_of() { return BLK == kBlockTrace ? kLdsNodes : PT_LDS_NODES_WIDE; }
 // wave-batched triangle tests (pt_device.h wave_tri_batch): 2.25 KB of LDS per wave
-// Trace kernels: 6 waves per SIMD (80 VGPRs, 3 spilled in cold paths); the textured variants
-// keep 4.
+// Trace kernels: 6 waves per SIMD (80 VGPRs, 3 spilled in cold paths)
 #ifndef PT_WF_WAVES
 #define PT_WF_WAVES 6
 #endif
 // the textured variants: 6 waves as well since round 6 (4 before; the textured atrium, config 5t,
-// +1.6 % at 6, ±0 at 5, profiles/r06_ab/r06m_ab_tex_c5t.log)
+// +1.6 % at 6, ±0 at 5, profiles/r06_ab/r06m_ab_tex_c5t.log).  They take the wide workgroups on
+// one-stream calls like the untextured ones (+0.7 % config 5t, +1.0 % on the small textured scene,
+// profiles/r06_ab/r06n_ab_widetex_*.log).
 #ifndef PT_WF_WAVES_TEX
 #define PT_WF_WAVES_TEX 6
-#endif
-// PT_WIDE_TEX 1: the textured trace kernels take the wide workgroups as well on one-stream calls
-#ifndef PT_WIDE_TEX
-#define PT_WIDE_TEX 1  // +0.7 % config 5t, +1.0 % on the small textured scene (profiles/r06_ab/r06n_ab_widetex_*.log)
 #endif
 constexpr int wf_waves(bool tex) { return tex ? PT_WF_WAVES_TEX : PT_WF_WAVES; }
 constexpr int kMissTri = -1;
@@ -160,8 +157,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     return v;
 }
 
-// Traversal statistics of a wave into the renderer's counters ([1] nodes, [2] triangle tests,
-// [3] rays, [4] stack overflows, [8] strict re-traces, [14] node visits served from LDS).
+// Traversal statistics of a wave into the renderer's counters (pt_device.h Counter).
 template <bool STATS>
 __device__ __forceinline__ void flush_trav_stats(unsigned long long* counters, const TravStats& ts) {
     if (!STATS || !counters) return;
@@ -169,20 +165,20 @@ __device__ __forceinline__ void flush_trav_stats(unsigned long long* counters, c
     const unsigned long long e = wave_sum_u64(ts.overflow), r = wave_sum_u64(ts.retrace);
     const unsigned long long l = wave_sum_u64(ts.lds_nodes), u = wave_sum_u64(ts.unocc);
     if (lane_id() == 0) {  // the wave-schedule counts are kept by every lane alike: lane 0's
-        atomicAdd(&counters[1], a);
-        atomicAdd(&counters[2], c);
-        atomicAdd(&counters[3], d);
-        atomicAdd(&counters[4], e);
-        atomicAdd(&counters[8], r);
-        atomicAdd(&counters[9], (unsigned long long)ts.steps);
-        atomicAdd(&counters[10], (unsigned long long)ts.active);
-        atomicAdd(&counters[11], (unsigned long long)ts.node_steps);
-        atomicAdd(&counters[12], (unsigned long long)ts.tri_steps);
-        atomicAdd(&counters[13], (unsigned long long)ts.refills);
-        atomicAdd(&counters[14], l);
-        atomicAdd(&counters[18], u);
-        for (int k = 0; k < 6; ++k) atomicAdd(&counters[20 + k], (unsigned long long)ts.coh[k]);
-        atomicAdd(&counters[26], (unsigned long long)ts.coh_lanes);
+        atomicAdd(&counters[kCtrNodes], a);
+        atomicAdd(&counters[kCtrTriTests], c);
+        atomicAdd(&counters[kCtrRays], d);
+        atomicAdd(&counters[kCtrStackOverflows], e);
+        atomicAdd(&counters[kCtrRetraces], r);
+        atomicAdd(&counters[kCtrWaveSteps], (unsigned long long)ts.steps);
+        atomicAdd(&counters[kCtrWaveActive], (unsigned long long)ts.active);
+        atomicAdd(&counters[kCtrWaveNodeSteps], (unsigned long long)ts.node_steps);
+        atomicAdd(&counters[kCtrWaveTriSteps], (unsigned long long)ts.tri_steps);
+        atomicAdd(&counters[kCtrWaveRefills], (unsigned long long)ts.refills);
+        atomicAdd(&counters[kCtrLdsNodes], l);
+        atomicAdd(&counters[kCtrNeeUnoccluded], u);
+        for (int k = 0; k < 6; ++k) atomicAdd(&counters[kCtrCoh0 + k], (unsigned long long)ts.coh[k]);
+        atomicAdd(&counters[kCtrCohLanes], (unsigned long long)ts.coh_lanes);
     }
 }
 
@@ -192,18 +188,15 @@ __device__ __forceinline__ void flush_trav_stats(unsigned long long* counters, c
 // kShadeBuckets BSDF-sample counters follow the two queue counters.
 constexpr int kShadeBuckets = 3;
 // NEE buckets (round 6): 0 = conductor; 1 = kNeeCross, layered items whose light lies across the
-// shading plane from the viewer (PT_NEE_CROSS), so that every other layered NEE wave runs the
-// walk's compile-time path (layered_f_split; without it 70 % of Sponza-class's and 45 % of
-// Layered's walk waves held such a lane, 4.2 / 1.6 % of the lanes, tools/nee_probe.py); then per
+// shading plane from the viewer, so that every other layered NEE wave runs the walk's
+// compile-time path (layered_f_split; without it 70 % of Sponza-class's and 45 % of Layered's
+// walk waves held such a lane, 4.2 / 1.6 % of the lanes); then per
 // albedo class k (kNeeClasses) the layered items with a smooth (2 + 2k) and a rough (3 + 2k) top.
 // The walk's Russian roulette ends walks over a dark bottom layer early, so a wave that mixes
 // them with bright ones runs as long as its brightest lane: the class of an item is the largest
 // channel of its albedo against PT_NEE_MID (classes >= 3) and PT_NEE_DARK (classes >= 2).
 // Bucket q fills region q / 2 of W.nq from the front (q even) or the back (q odd): a bounce
 // queues at most W.paths NEE items in all, so the two ends of a region never meet.
-#ifndef PT_NEE_CROSS
-#define PT_NEE_CROSS 1
-#endif
 #ifndef PT_NEE_CLASSES
 #define PT_NEE_CLASSES 2
 #endif
@@ -218,18 +211,12 @@ constexpr int kNeeBuckets = 2 + 2 * kNeeClasses;
 constexpr int kNeeRegions = kNeeBuckets / 2;
 constexpr int kNeeCross = 1;
 static_assert(kNeeBuckets <= 8, "a shadow ray's item code holds the NEE bucket in bits 28-30");
-// PT_SMP_DARK (> 0): a dark class of the BSDF-sample items, as PT_NEE_DARK (not kept):
-// kSmpDark0 + 0 / 1 beside buckets 1 / 2, from the back of regions 1 / 2 of W.sq
-#ifndef PT_SMP_DARK
-#define PT_SMP_DARK 0.0f
-#endif
-constexpr bool kSmpDark = PT_SMP_DARK > 0.0f;
-constexpr int kSmpBuckets = kShadeBuckets + (kSmpDark ? 2 : 0);
-constexpr int kSmpDark0 = kShadeBuckets;
-constexpr int kCnt = 5 + kNeeBuckets + kSmpBuckets;
+// (The BSDF-sample items keep the kShadeBuckets sample buckets: a dark class of them, as
+// PT_NEE_DARK for the NEE items, was not kept)
+constexpr int kCnt = 5 + kNeeBuckets + kShadeBuckets;
 constexpr int kCntStride = 32;  // ints per counter = 128 B
 // kPool*: the run-time ray pools of k_trace_pair, k_extend and k_shadow_vis (RayPool)
-enum { kQueue = 0, kShadowQ = 1, kNee0 = 2, kSmp0 = 2 + kNeeBuckets, kPool = 2 + kNeeBuckets + kSmpBuckets, kPoolExt, kPoolSh };
+enum { kQueue = 0, kShadowQ = 1, kNee0 = 2, kSmp0 = 2 + kNeeBuckets, kPool = 2 + kNeeBuckets + kShadeBuckets, kPoolExt, kPoolSh };
 __device__ __forceinline__ int* cnt(const WFState& W, int b, int k) { return W.count + (kCnt * b + k) * kCntStride; }
 // Slot `slot` of NEE bucket q in W.nq
 __device__ __forceinline__ size_t nee_index(const WFState& W, int q, int slot) {
@@ -244,11 +231,9 @@ __device__ __forceinline__ int nee_layered_bucket(int bk, f3 albedo) {
     if (kNeeClasses >= 2 && m < PT_NEE_DARK) cls = kNeeClasses - 1;
     return 2 + 2 * cls + (bk - 1);
 }
-// Slot `slot` of sample bucket q in W.sq: region q from the front, the dark buckets from the back
-// of regions 1 / 2
+// Slot `slot` of sample bucket q in W.sq: region q from the front
 __device__ __forceinline__ size_t smp_index(const WFState& W, int q, int slot) {
-    if (q < kShadeBuckets) return (size_t)q * W.paths + slot;
-    return (size_t)(q - kSmpDark0 + 2) * W.paths - 1 - slot;
+    return (size_t)q * W.paths + slot;
 }
 // Path throughput | seed.  W.beta in path order (the phases of a bounce read it by path), except
 // in the Lambert mode: in queue order next to the ray, ping-pong like ray_o / ray_d (queue b
@@ -313,12 +298,8 @@ constexpr int shf_block(int mode) {
 #endif
 constexpr int kBlockShB = PT_SHB_BLOCK;
 
-#ifndef PT_NEE_LEAN
-#define PT_NEE_LEAN 1  // k_shade_nee keeps four values live across the walk
-#endif
-
 // Block-wide compaction: every thread of the block calls this (uniform control flow);
-// threads with pred get consecutive slots.  `lds` is kWavesSh + 1 ints of shared memory
+// threads with pred get consecutive slots.  `lds` is WAVES + 1 ints of shared memory
 // private to this call site.
 template <int WAVES>
 __device__ __forceinline__ int block_append(int* counter, bool pred, int* lds) {
@@ -339,58 +320,6 @@ __device__ __forceinline__ int block_append(int* counter, bool pred, int* lds) {
     __syncthreads();
     return lds[WAVES] + lds[wave] + prefix;
 }
-
-// Block-wide append with one atomic per block whose slots are ordered by key: the block's range
-// holds its key-0 items first, then key 1, ... (thread order within a key); key < 0 appends
-// nothing.  Consecutive queue entries then share their key (the shadow rays' light, the
-// continuation rays' direction octant), so the trace kernels' waves trace rays that take similar
-// paths through the BVH.  `lds` holds K * WAVES + K + 1 ints.
-template <int WAVES, int K>
-__device__ __forceinline__ int block_append_sorted(int* counter, int key, int* lds) {
-    const int wave = threadIdx.x >> 6;
-    unsigned long long mine = 0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const unsigned long long m = __ballot(key == k ? 1 : 0);
-        if (key == k) mine = m;
-        if (lane_id() == 0) lds[k * WAVES + wave] = __popcll(m);
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < K) {  // per key: the waves' exclusive prefix and the key's total
-        const int k = threadIdx.x;
-        int tot = 0;
-        for (int w = 0; w < WAVES; ++w) {
-            const int c = lds[k * WAVES + w];
-            lds[k * WAVES + w] = tot;
-            tot += c;
-        }
-        lds[K * WAVES + 1 + k] = tot;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {  // the keys' exclusive prefix, one atomic for the block
-        int tot = 0;
-        for (int k = 0; k < K; ++k) {
-            const int c = lds[K * WAVES + 1 + k];
-            lds[K * WAVES + 1 + k] = tot;
-            tot += c;
-        }
-        lds[K * WAVES] = tot > 0 ? atomicAdd(counter, tot) : 0;
-    }
-    __syncthreads();
-    if (key < 0) return 0;
-    const int pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
-    return lds[K * WAVES] + lds[K * WAVES + 1 + key] + lds[key * WAVES + wave] + pre;
-}
-// PT_SORT_SHADOW / PT_SORT_EXT: the fused shading kernels append their shadow rays ordered by light
-// and their continuation rays ordered by direction octant within each block (block_append_sorted)
-#ifndef PT_SORT_SHADOW
-#define PT_SORT_SHADOW 0
-#endif
-#ifndef PT_SORT_EXT
-#define PT_SORT_EXT 0
-#endif
-constexpr int kSortKeys = 8;
-__device__ __forceinline__ int octant(f3 d) { return (d.x < 0.0f ? 1 : 0) | (d.y < 0.0f ? 2 : 0) | (d.z < 0.0f ? 4 : 0); }
 
 // Block-wide append into K bucket regions (counter of bucket k at counter0 + k * kCntStride):
 // threads with bucket k in [0, K) get consecutive slots of region k in thread order, bucket < 0
@@ -468,63 +397,34 @@ __global__ __launch_bounds__(kBlockWF) void k_camera(WFState W, DevLaunch L, uin
     if (blockIdx.x == 0 && threadIdx.x == 0) *cnt(W, 0, kQueue) = Q;
 }
 
-// This wave's static slice of a queue of length n (grid sized to residency, so every wave
-// is resident and slices balance statistically; no fetch atomics).
 #ifndef PT_REFILL_MIN
 #define PT_REFILL_MIN 16  // idle lanes before a wave refills (24 before the triangle batches;
                           // with them 12 / 16 / 20 / 32: -1 / 0 / -0 / -5 %)
 #endif
 constexpr int kRefillMin = PT_REFILL_MIN;
-#ifndef PT_SPLIT_FINISH  // k_trace_pair's deferred NEE add as load + store around the refill:
-#define PT_SPLIT_FINISH 1  // +2.2 % Lambert, +1.3 % Conductor, +0.4 % Dielectric
-#endif
 
 #ifndef PT_TRI_BATCH
 #define PT_TRI_BATCH 20  // lanes with a pending leaf before a wave runs its triangle batch (8 / 12 / 16 /
                          // 20 / 24 / 32: -7 / -2 / -0.3 / 0 / -0.3 / -5 %)
 #endif
 
-// chunk_log = k > 0: the queue is cut into chunks of 2^k rays dealt round-robin to the waves,
-// so every wave's share samples the whole queue instead of one contiguous stretch of image rows
-// (whose cost differs from the next stretch's).  A wave then walks a virtual range [0, count) of
-// its chunks, and slice_ray maps a virtual index to the queue index.  k_extend and k_shadow_vis
-// use PT_SLICE_CHUNK_LOG_X, k_trace_pair contiguous slices.
-#ifndef PT_SLICE_CHUNK_LOG
-#define PT_SLICE_CHUNK_LOG 0
-#endif
-#ifndef PT_SLICE_CHUNK_LOG_X
-#define PT_SLICE_CHUNK_LOG_X PT_SLICE_CHUNK_LOG
-#endif
-__device__ __forceinline__ void wave_slice(int n, int& first, int& end, int chunk_log = 0) {
+// This wave's static slice of a queue of length n (grid sized to residency, so every wave
+// is resident and slices balance statistically; no fetch atomics).  Slices are contiguous: chunks
+// dealt round-robin to the waves were not kept.
+__device__ __forceinline__ void wave_slice(int n, int& first, int& end) {
     const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const int nwaves = (int)((gridDim.x * blockDim.x) >> 6);
-    if (chunk_log > 0) {
-        const int K = 1 << chunk_log;
-        const int chunks = (n + K - 1) / K;
-        const int mine = chunks > wave ? (chunks - 1 - wave) / nwaves + 1 : 0;
-        first = 0;
-        // only the queue's last chunk is partial, and it is the last chunk of its wave
-        end = mine * K - ((chunks > 0 && (chunks - 1) % nwaves == wave) ? chunks * K - n : 0);
-        return;
-    }
     const int per = (n + nwaves - 1) / nwaves;
     first = min(n, wave * per);
     end = min(n, first + per);
 }
-// queue index of the wave's virtual index v (identity without chunks)
-__device__ __forceinline__ int slice_ray(int v, int chunk_log) {
-    if (chunk_log == 0) return v;
-    const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const int nwaves = (int)((gridDim.x * blockDim.x) >> 6);
-    return (((v >> chunk_log) * nwaves + wave) << chunk_log) + (v & ((1 << chunk_log) - 1));
-}
 
 typedef float pt_v4f __attribute__((ext_vector_type(4)));
-// k_shade_fused (the memory-bound kernel of a fused-mode frame, ≈ 66 % of HBM peak) streams
-// its queue records and the path state once: non-temporal loads and stores keep them from
-// evicting the triangle and material lines its gathers reuse.  Lambert +2 %, Dielectric and
-// Conductor +0.4 %.  (The same hint on the trace kernels' queues: ±0.5 %, not
-// used -- they are not memory-bound.)
+// Queue records that a kernel streams once are loaded and stored non-temporally, so that they do
+// not evict the lines its gathers reuse.  k_shade_fused and k_shade0_pixel (memory-bound, ≈ 66 % of
+// HBM peak): Lambert +2 %, Dielectric and Conductor +0.4 %.  k_trace_pair: 19 % less traffic of
+// its own, rate ±0.2 %.  k_extend and k_shadow_vis use plain loads and stores (configs 3 / 5
+// +0.1 / +0.3 %, Lambert -0.6 % with the hint: not kept).  DESIGN.md §5.
 __device__ __forceinline__ float4 ldqs(const float4* p) {
     const pt_v4f v = __builtin_nontemporal_load(reinterpret_cast<const pt_v4f*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
@@ -533,82 +433,11 @@ __device__ __forceinline__ void stqs(float4* p, float4 v) {
     __builtin_nontemporal_store(pt_v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<pt_v4f*>(p));
 }
 
-// k_trace_pair's queue records (DESIGN.md §5 "Where k_trace_pair's memory traffic goes"):
-// PT_TRACE_NTQ = 1 loads and stores them non-temporally; PT_PROBE_NO_NEE_ADD = 1 drops the deferred
-// NEE add (a measurement probe: wrong images, same rays).
-#ifndef PT_TRACE_NTQ
-#define PT_TRACE_NTQ 1  // 19 % less k_trace_pair traffic, rate ±0.2 %
-#endif
-#ifndef PT_PROBE_NO_NEE_ADD
-#define PT_PROBE_NO_NEE_ADD 0
-#endif
-// How an unoccluded shadow ray of k_trace_pair adds its contribution to W.L[path]: 0 = load in
-// finish + store in commit (v37); 1 = three no-return float atomics; 2 = the ray only writes its
-// path (or -1) into its own sh_c record and k_nee_add adds in shadow-queue order after the launch.
-#ifndef PT_NEE_MODE
-#define PT_NEE_MODE 0
-#endif
-__device__ __forceinline__ float4 ldq_pair(const float4* p) { return PT_TRACE_NTQ ? ldqs(p) : *p; }
-// the same for k_extend and k_shadow_vis (PT_TRACE_NTQ_X)
-#ifndef PT_TRACE_NTQ_X
-#define PT_TRACE_NTQ_X 0  // configs 3 / 5 +0.1 / +0.3 %, Lambert -0.6 %: not kept
-#endif
-__device__ __forceinline__ float4 ldq_x(const float4* p) { return PT_TRACE_NTQ_X ? ldqs(p) : *p; }
-__device__ __forceinline__ void stq_x(float4* p, float4 v) {
-    if (PT_TRACE_NTQ_X)
-        stqs(p, v);
-    else
-        *p = v;
-}
-__device__ __forceinline__ void stq_pair(float4* p, float4 v) {
-    if (PT_TRACE_NTQ)
-        stqs(p, v);
-    else
-        *p = v;
-}
-
-// PT_TAIL_PROBE = 1 (measurement only): every k_trace_pair wave adds its start and end times
-// (s_memrealtime, 100 MHz) to module counters, and the last wave of the launch prints the launch
-// span, the waves' mean lifetime and the spread of their end times, so the static slices' tail
-// can be read off.
-#ifndef PT_TAIL_PROBE
-#define PT_TAIL_PROBE 0
-#endif
-#if PT_TAIL_PROBE
-__device__ unsigned long long g_tail[5];  // ~min start, max end, sum end, finished waves, sum start
-__device__ __forceinline__ void tail_probe_begin(unsigned long long& t0) {
-    t0 = __builtin_amdgcn_s_memrealtime();
-    if ((threadIdx.x & 63) == 0) {
-        atomicMax(&g_tail[0], ~t0);
-        atomicAdd(&g_tail[4], t0);
-    }
-}
-__device__ __forceinline__ void tail_probe_end(int b) {
-    const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-    if ((threadIdx.x & 63) != 0) return;
-    atomicMax(&g_tail[1], t1);
-    atomicAdd(&g_tail[2], t1);
-    __threadfence();
-    const unsigned long long nw = (unsigned long long)gridDim.x * (blockDim.x / 64);
-    if (atomicAdd(&g_tail[3], 1ull) == nw - 1) {
-        __threadfence();
-        const unsigned long long t0 = ~atomicAdd(&g_tail[0], 0ull), te = atomicAdd(&g_tail[1], 0ull);
-        const unsigned long long se = atomicAdd(&g_tail[2], 0ull), ss = atomicAdd(&g_tail[4], 0ull);
-        const double mean_end = (double)se / (double)nw - (double)t0, mean_start = (double)ss / (double)nw - (double)t0;
-        printf("TAIL b=%d waves=%llu span_us=%.1f mean_start_us=%.1f mean_end_us=%.1f idle_frac=%.4f\n", b, nw,
-               (double)(te - t0) / 100.0, mean_start / 100.0, mean_end / 100.0,
-               1.0 - (mean_end - mean_start) / (double)(te - t0));
-        for (int k = 0; k < 5; ++k) atomicExch(&g_tail[k], 0ull);  // vector atomics, no plain stores
-        __threadfence();
-    }
-}
-#endif
-
 // Lane-refilling trace loop over a queue slice: `fetch(ri, state)` initialises lane state
 // for ray ri, `finish(ri, state)` consumes a finished ray.  A finish that returns a token is
 // split in two: its loads are issued before the refill's record loads and `commit(token)` (its
 // stores) runs after them, so the two memory round trips of a batch block overlap
-// (PT_SPLIT_FINISH).  A lane whose traversal ends parks
+// (DESIGN.md §5).  A lane whose traversal ends parks
 // (`done`) until enough lanes are idle; then the wave runs one batch block that finishes the
 // parked rays and refills the idle lanes with the next rays of the slice.  The triangle
 // batches take acceptable hits only (wave_tri_batch), so a finished ray's answer is final.
@@ -636,7 +465,6 @@ __device__ __forceinline__ bool pool_pays(int n) {
 struct RayPool {
     int* ctr = nullptr;
     int begin = 0, end = 0;
-    int chunk_log = 0;  // the static slices' chunk interleave (wave_slice)
 };
 
 struct NoCommit {
@@ -664,7 +492,6 @@ __device__ __forceinline__ void trace_range(const DevScene& S, int next, int end
     // in eight workgroups relays the host word at every 64th
     uint32_t npoll = 0;
     int* pctr = pool.ctr;
-    int vlog = pool.chunk_log;  // the static slice walks chunk-interleaved virtual indices
     if (W.cancel_seen && wf_cancel_poll(W, false)) {
         end = next;
         pctr = nullptr;
@@ -682,7 +509,6 @@ __device__ __forceinline__ void trace_range(const DevScene& S, int next, int end
                 int base = 0;
                 if ((threadIdx.x & 63) == 0) base = atomicAdd(pctr, PT_POOL_CHUNK);
                 base = __builtin_amdgcn_readfirstlane(__shfl(base, 0, 64));
-                vlog = 0;
                 next = min(pool.begin + base, pool.end);
                 end = min(next + PT_POOL_CHUNK, pool.end);
                 if (next >= pool.end) pctr = nullptr;
@@ -705,7 +531,7 @@ __device__ __forceinline__ void trace_range(const DevScene& S, int next, int end
             const unsigned long long m = __ballot(ri < 0);
             const int pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             if (ri < 0 && next + pre < end) {
-                ri = vlog ? slice_ray(next + pre, vlog) : next + pre;
+                ri = next + pre;
                 fetch(ri, st);
                 if (STATS) ts.rays++;
                 done = S.ntri <= 0;  // empty scene: no BVH root, every ray misses
@@ -797,7 +623,6 @@ __device__ __forceinline__ void trace_slice(const DevScene& S, int n, TravStats&
                                             Finish finish, int* pool_ctr) {
     int next, end;
     RayPool pool;
-    pool.chunk_log = PT_SLICE_CHUNK_LOG_X;
     pool.end = n;
     if (PT_TRACE_POOL_X > 0 && pool_pays(n)) {
         pool.ctr = pool_ctr;
@@ -805,7 +630,7 @@ __device__ __forceinline__ void trace_slice(const DevScene& S, int n, TravStats&
     } else {
         pool.begin = n;
     }
-    wave_slice(pool.begin, next, end, pool.chunk_log);
+    wave_slice(pool.begin, next, end);
     trace_queue<ANY, STATS, TEX, BLK>(S, next, end, ts, W, fetch, finish, NoCommit{}, pool);
 }
 
@@ -825,20 +650,22 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_extend(DevScene S, WFSta
     trace_slice<kRayClosest, STATS, TEX, BLK>(
         S, n_trace, ts, W,
         [&](int ri, TravState& st) {
-            const float4 a = ldq_x(ro + ri), c = ldq_x(rd + ri);
+            const float4 a = ro[ri], c = rd[ri];
             trav_init(st, mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), 0.0f, 100.0f);
             st.path = __float_as_int(a.w);
         },
         [&](int ri, const TravState& st) {
             // copy k of a bounce-0 ray is path st.path + k * n_trace (queue 0 is in path order);
             // copies = 1: k_shade0_pixel reads the pixel's one record for all its frames
-            for (int k = 0; k < copies; ++k)
-                stq_x(W.hit + ri + (size_t)k * n_trace, hit_record(st.h, st.path + k * n_trace));
+            for (int k = 0; k < copies; ++k) {
+                float4* rec = W.hit + ri + (size_t)k * n_trace;
+                *rec = hit_record(st.h, st.path + k * n_trace);
+            }
         }, cnt(W, b, kPoolExt));
     if (blockIdx.x == 0 && threadIdx.x == 0 && counters) {
-        atomicAdd(&counters[0], (unsigned long long)n);        // path segments
-        atomicAdd(&counters[6], (unsigned long long)n_trace);  // rays traced by the timed trace kernels
-        atomicAdd(&counters[7], (32ull + 16ull * (unsigned long long)copies) * (unsigned long long)n_trace);  // bytes
+        atomicAdd(&counters[kCtrSegments], (unsigned long long)n);
+        atomicAdd(&counters[kCtrTraceRays], (unsigned long long)n_trace);
+        atomicAdd(&counters[kCtrTraceBytes], (32ull + 16ull * (unsigned long long)copies) * (unsigned long long)n_trace);
     }
     flush_trav_stats<STATS>(counters, ts);
 }
@@ -894,7 +721,7 @@ __device__ __forceinline__ void lit_count_wave(bool answered, int* lds) {
     const unsigned long long m = __ballot(answered ? 1 : 0);
     if (lane_id() == 0) lds[threadIdx.x >> 6] = __popcll(m);
 }
-template <int WAVES, int SLOT = 27>
+template <int WAVES, int SLOT = kCtrLitAnswers>
 __device__ __forceinline__ void lit_count_block(const DevLaunch& L, const int* lds) {
     if (threadIdx.x != 0 || !L.counters) return;
     int tot = 0;
@@ -908,8 +735,7 @@ __device__ __forceinline__ void lit_count_block(const DevLaunch& L, const int* l
 // k_shadow_vis would answer "occluded": they reach that triangle (every BVH box that holds it
 // contains its padded box) or stop earlier at another hit.  That holds for ANY entry, so a stale or
 // wrong one only costs the test.  A cut-out triangle (E2.w != 0, alpha_cut may drop its hits in the
-// textured kernels) never answers.  pt_stats.occluder_table_answers counts them (slot 28).
-constexpr int kOccCounter = 28;
+// textured kernels) never answers.  pt_stats.occluder_table_answers counts them (kCtrOccAnswers).
 template <bool TEX>
 __device__ __forceinline__ bool occ_answers(const DevScene& S, int t, f3 o, f3 d, float tmax) {
     if (t < 0) return false;
@@ -976,7 +802,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
     const float4* rd = W.ray_d[b & 1];
     float4* no = W.ray_o[(b + 1) & 1];
     float4* nd = W.ray_d[(b + 1) & 1];
-    __shared__ int lds_sh[kSortKeys * kWaves + kSortKeys + 1], lds_q[kSortKeys * kWaves + kSortKeys + 1];
+    __shared__ int lds_sh[kWaves + 1], lds_q[kWaves + 1];
     __shared__ int lds_lit[kWaves];
     // the occluder candidates: Lambert only -- the register-bound Conductor and Dielectric kernels
     // spill more with the code present even when the table is off
@@ -984,7 +810,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
     __shared__ int lds_occ[kOcc ? kWaves : 1];
     const bool lit = !vis0 && L.lit_tri;  // the lit table answers this bounce's NEE tests where it can
     const bool occ = kOcc && lit && L.occ_tab;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && L.counters) atomicAdd(&L.counters[15], (unsigned long long)n);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && L.counters) atomicAdd(&L.counters[kCtrShadeItems], (unsigned long long)n);
     if ((int)(blockIdx.x * kBlock) >= n) return;  // block-uniform
     {
         const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
@@ -995,7 +821,6 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
         uint32_t seed = 0;
         float stmax = 0.0f;
         int path = 0;
-        int shadow_light = 0;
         int occ_t = -1;  // the shadow ray's entry of the occluder table: -1 or a triangle
         const int P1 = L.width * L.height;
         float4 l0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // shade0: the path's radiance after bounce 0
@@ -1057,7 +882,6 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
                             sdir = normalize(ldir);
                             stmax = length(ldir);
                             emit_shadow = true;
-                            shadow_light = li;
                             if (kOcc && occ && lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta)
                                 occ_t = L.occ_tab[li * (int)L.lit_cells + lit_c];  // lands while the BSDF is sampled
                         }
@@ -1074,8 +898,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
         }
         if (shade0 && valid) W.L[path] = l0;  // every path of the batch, hit or miss
         if (lit) lit_count_wave(lit_answer, lds_lit);
-        const int qi = PT_SORT_EXT ? block_append_sorted<kWaves, kSortKeys>(cnt(W, b + 1, kQueue), emit_next ? octant(d) : -1, lds_q)
-                                   : block_append<kWaves>(cnt(W, b + 1, kQueue), emit_next, lds_q);
+        const int qi = block_append<kWaves>(cnt(W, b + 1, kQueue), emit_next, lds_q);
         if (lit) lit_count_block<kWaves>(L, lds_lit);
         if (emit_next) {
             stqs(no + qi, make_float4(o.x, o.y, o.z, __int_as_float(path)));
@@ -1095,11 +918,9 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
                 lit_count_wave(answered, lds_occ);
             }
         }
-        const int si = PT_SORT_SHADOW ? block_append_sorted<kWaves, kSortKeys>(cnt(W, b, kShadowQ),
-                                                                              emit_shadow ? (shadow_light & (kSortKeys - 1)) : -1, lds_sh)
-                                      : block_append<kWaves>(cnt(W, b, kShadowQ), emit_shadow, lds_sh);
+        const int si = block_append<kWaves>(cnt(W, b, kShadowQ), emit_shadow, lds_sh);
         if constexpr (kOcc) {
-            if (occ) lit_count_block<kWaves, kOccCounter>(L, lds_occ);
+            if (occ) lit_count_block<kWaves, kCtrOccAnswers>(L, lds_occ);
         }
         if (emit_shadow) {
             // Lambert: a sampled direction is never below the surface (lambert_sample forces z >= 0),
@@ -1124,9 +945,9 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
     constexpr bool kBetaQ = MODE == kModeLambert;  // as k_shade_fused
     constexpr int kBlock = shf_block(MODE), kWaves = kBlock / 64;
     const int P1 = L.width * L.height;
-    __shared__ int lds_q[kSortKeys * kWaves + kSortKeys + 1];
+    __shared__ int lds_q[kWaves + 1];
     if (blockIdx.x == 0 && threadIdx.x == 0 && L.counters)
-        atomicAdd(&L.counters[15], (unsigned long long)P1 * (unsigned long long)nf);
+        atomicAdd(&L.counters[kCtrShadeItems], (unsigned long long)P1 * (unsigned long long)nf);
     if ((int)(blockIdx.x * kBlock) >= P1) return;  // block-uniform
     const int p = (int)(blockIdx.x * kBlock + threadIdx.x);
     const bool valid = p < P1 && !wf_cancelled(W);  // a cancelled wave still joins the appends
@@ -1177,8 +998,7 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
             }
         }
         if (valid) stqs(W.L + path, l0);  // every path of the batch, hit or miss
-        const int qi = PT_SORT_EXT ? block_append_sorted<kWaves, kSortKeys>(cnt(W, 1, kQueue), emit_next ? octant(d) : -1, lds_q)
-                                   : block_append<kWaves>(cnt(W, 1, kQueue), emit_next, lds_q);
+        const int qi = block_append<kWaves>(cnt(W, 1, kQueue), emit_next, lds_q);
         if (emit_next) {
             stqs(no + qi, make_float4(o.x, o.y, o.z, __int_as_float(path)));
             stqs(nd + qi, make_float4(d.x, d.y, d.z, 0.0f));
@@ -1194,10 +1014,6 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
 template <bool STATS, bool TEX, int BLK = kBlockTrace>
 __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, WFState W, int b,
                                                                       unsigned long long* counters) {
-#if PT_TAIL_PROBE
-    unsigned long long tp0;
-    tail_probe_begin(tp0);
-#endif
     const int n_ext = *cnt(W, b + 1, kQueue);
     const int n_sh = *cnt(W, b, kShadowQ);
     const float4* ro = W.ray_o[(b + 1) & 1];
@@ -1205,16 +1021,16 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
     TravStats ts;
     auto fetch = [&](int i, TravState& st) {
         if (i < n_ext) {
-            const float4 a = ldq_pair(ro + i), c = ldq_pair(rd + i);
+            const float4 a = ldqs(ro + i), c = ldqs(rd + i);
             trav_init(st, mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), 0.0f, 100.0f);
             st.path = __float_as_int(a.w);
         } else {
             const int j = i - n_ext;
-            const float4 c = ldq_pair(W.sh_d + j), k = ldq_pair(W.sh_c + j);
+            const float4 c = ldqs(W.sh_d + j), k = ldqs(W.sh_c + j);
             // origin | path: the shadow ray's own record, or (Lambert) the continuation ray of the
             // same path, which starts at the same point (k_shade_fused)
             const int q = __float_as_int(k.w);
-            const float4 a = ldq_pair(q >= 0 ? ro + q : W.sh_o + j);
+            const float4 a = ldqs(q >= 0 ? ro + q : W.sh_o + j);
             trav_init(st, mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), 0.0f, c.w);
             st.any = true;
             // an any-hit traversal only writes h.tri: the record's other fields carry the path
@@ -1225,7 +1041,6 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
             st.h.v = k.z;
         }
     };
-#if PT_SPLIT_FINISH
     // the deferred NEE add as load (finish, before the refill's record loads) + store (commit,
     // after them): the lane does not wait for the radiance line before the refill
     struct NeeAdd {
@@ -1237,14 +1052,12 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
         NeeAdd a{nullptr, make_float4(0.0f, 0.0f, 0.0f, 0.0f), 0.0f, 0.0f, 0.0f};
         const Hit& h = st.h;
         // the hit-record stores first: a store issued after the radiance load would wait for it
-        if (i < n_ext) stq_pair(W.hit + i, hit_record(h, st.path));
+        if (i < n_ext) stqs(W.hit + i, hit_record(h, st.path));
         __builtin_amdgcn_sched_barrier(0);
         if (STATS && i >= n_ext && h.tri < 0) ts.unocc++;
-        if (PT_NEE_MODE == 2 && !PT_PROBE_NO_NEE_ADD && i >= n_ext)  // k_nee_add adds
-            reinterpret_cast<int*>(W.sh_c + (i - n_ext))[3] = h.tri < 0 ? h.orig : -1;
-        if (PT_NEE_MODE != 2 && !PT_PROBE_NO_NEE_ADD && i >= n_ext && h.tri < 0) {  // unoccluded: add the deferred NEE contribution
+        if (i >= n_ext && h.tri < 0) {  // unoccluded: add the deferred NEE contribution
             a.p = W.L + h.orig;
-            if (PT_NEE_MODE == 0) a.v = *a.p;
+            a.v = *a.p;
             a.x = h.t;
             a.y = h.u;
             a.z = h.v;
@@ -1252,27 +1065,8 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
         return a;
     };
     auto commit = [&](const NeeAdd& a) {
-        if (PT_NEE_MODE == 1 && a.p) {
-            float* f = reinterpret_cast<float*>(a.p);
-            __hip_atomic_fetch_add(f + 0, a.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(f + 1, a.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(f + 2, a.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else if (a.p) {
-            *a.p = make_float4(a.v.x + a.x, a.v.y + a.y, a.v.z + a.z, 0.0f);
-        }
+        if (a.p) *a.p = make_float4(a.v.x + a.x, a.v.y + a.y, a.v.z + a.z, 0.0f);
     };
-#else
-    auto finish = [&](int i, const TravState& st) {
-        const Hit& h = st.h;
-        if (i < n_ext) {
-            W.hit[i] = hit_record(h, st.path);
-        } else if (h.tri < 0) {  // unoccluded: add the deferred NEE contribution
-            const float4 l = W.L[h.orig];
-            W.L[h.orig] = make_float4(l.x + h.t, l.y + h.u, l.z + h.v, 0.0f);
-        }
-    };
-    auto commit = NoCommit{};
-#endif
     // The queue is [extension rays | shadow rays] in contiguous wave slices, so all but one wave
     // trace a single ray kind; a mixed-kind loop serves both (per-kind loops in one kernel and
     // per-wave shares of both kinds were slower).
@@ -1288,17 +1082,14 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
     }
     wave_slice(pool.begin, first, end);
     trace_queue<kRayMixed, STATS, TEX, BLK>(S, first, end, ts, W, fetch, finish, commit, pool);
-#if PT_TAIL_PROBE
-    tail_probe_end(b);
-#endif
     if (blockIdx.x == 0 && threadIdx.x == 0 && counters) {
-        atomicAdd(&counters[0], (unsigned long long)n_ext);           // path segments
-        atomicAdd(&counters[5], (unsigned long long)n_sh);            // shadow rays
-        atomicAdd(&counters[6], (unsigned long long)(n_ext + n_sh));  // rays of timed trace kernels
-        atomicAdd(&counters[7], 48ull * (unsigned long long)(n_ext + n_sh));  // their queue bytes
-        atomicAdd(&counters[16], (unsigned long long)(n_ext + n_sh));         // the same, k_trace_pair alone
-        atomicAdd(&counters[17], 48ull * (unsigned long long)(n_ext + n_sh));
-        atomicAdd(&counters[19], (unsigned long long)n_sh);
+        atomicAdd(&counters[kCtrSegments], (unsigned long long)n_ext);
+        atomicAdd(&counters[kCtrShadowRays], (unsigned long long)n_sh);
+        atomicAdd(&counters[kCtrTraceRays], (unsigned long long)(n_ext + n_sh));
+        atomicAdd(&counters[kCtrTraceBytes], 48ull * (unsigned long long)(n_ext + n_sh));  // their queue bytes
+        atomicAdd(&counters[kCtrPairRays], (unsigned long long)(n_ext + n_sh));
+        atomicAdd(&counters[kCtrPairBytes], 48ull * (unsigned long long)(n_ext + n_sh));
+        atomicAdd(&counters[kCtrPairShadowRays], (unsigned long long)n_sh);
     }
     flush_trav_stats<STATS>(counters, ts);
 }
@@ -1313,7 +1104,7 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
     const int n = *cnt(W, b, kQueue);
     const float4* rd = W.ray_d[b & 1];
     __shared__ int lds_sh[kWavesShA + 1];
-    __shared__ int lds_nee[kNeeBuckets * (kWavesShA + 1)], lds_smp[kSmpBuckets * (kWavesShA + 1)];
+    __shared__ int lds_nee[kNeeBuckets * (kWavesShA + 1)], lds_smp[kShadeBuckets * (kWavesShA + 1)];
     __shared__ int lds_lit[kWavesShA], lds_occ[kWavesShA];
     const bool lit = !vis0 && L.lit_tri;  // as k_shade_fused
     const bool occ = lit && L.occ_tab;    // the occluder candidates (occ_answers)
@@ -1346,20 +1137,14 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
             W.aux[path] = (li << 1) | (conductor ? 1 : 0);
             const int bk = shade_bucket<MODE>(conductor, sf.roughness);
             // the last bounce's sampled direction is never traced (SamplePath :646): no sample item
-            if (b + 1 < L.max_bounces) {
-                smp_bucket = bk;
-                if (kSmpDark && (MODE == kModeLayered || !conductor) &&
-                    fmaxf(fmaxf(sf.albedo.x, sf.albedo.y), sf.albedo.z) < PT_SMP_DARK)
-                    smp_bucket = kSmpDark0 + bk - 1;
-            }
+            if (b + 1 < L.max_bounces) smp_bucket = bk;
             if (P > 0.0f) {
                 const DevLight lt = L.lights[li];
                 f3 ldir = mk(lt.px, lt.py, lt.pz) - sf.pos;
                 const f3 ln = normalize(ldir);  // k_shade_nee's light direction, the same bits
                 int nb = 0;  // conductor
                 if (MODE == kModeLayered || !conductor)
-                    nb = PT_NEE_CROSS && !same_hemisphere(sf.wo, to_local(sf.fr, ln)) ? kNeeCross
-                                                                                     : nee_layered_bucket(bk, sf.albedo);
+                    nb = !same_hemisphere(sf.wo, to_local(sf.fr, ln)) ? kNeeCross : nee_layered_bucket(bk, sf.albedo);
                 // the lit table: known unoccluded, straight to the NEE queue like the bounce-0 table
                 lit_answer = lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta && lit_bit(L, li, lit_c);
                 if (vis0 || lit_answer) {
@@ -1382,14 +1167,14 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
     if (occ) lit_count_wave(occ_answer, lds_occ);
     const int si = block_append<kWavesShA>(cnt(W, b, kShadowQ), emit, lds_sh);
     if (lit) lit_count_block<kWavesShA>(L, lds_lit);
-    if (occ) lit_count_block<kWavesShA, kOccCounter>(L, lds_occ);
+    if (occ) lit_count_block<kWavesShA, kCtrOccAnswers>(L, lds_occ);
     if (emit) {
         W.sh_o[si] = make_float4(so.x, so.y, so.z, __int_as_float(code));
         W.sh_d[si] = make_float4(sdir.x, sdir.y, sdir.z, stmax);
     }
     const int ni = block_append_k<kWavesShA, kNeeBuckets>(cnt(W, b, kNee0), nee_bucket, lds_nee);
     if (nee_bucket >= 0) W.nq[nee_index(W, nee_bucket, ni)] = i;
-    const int mi = block_append_k<kWavesShA, kSmpBuckets>(cnt(W, b, kSmp0), smp_bucket, lds_smp);
+    const int mi = block_append_k<kWavesShA, kShadeBuckets>(cnt(W, b, kSmp0), smp_bucket, lds_smp);
     if (smp_bucket >= 0) W.sq[smp_index(W, smp_bucket, mi)] = i;
 }
 
@@ -1400,12 +1185,12 @@ template <bool TEX, int BLK = kBlockTrace>
 __global__ __launch_bounds__(BLK, wf_waves(false)) void k_shadow_vis(DevScene S, WFState W, int b, int table,
                                                                       unsigned long long* counters) {
     const int n = *cnt(W, b, kShadowQ);
-    if (blockIdx.x == 0 && threadIdx.x == 0 && counters) atomicAdd(&counters[5], (unsigned long long)n);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && counters) atomicAdd(&counters[kCtrShadowRays], (unsigned long long)n);
     TravStats ts;
     trace_slice<kRayAny, false, TEX, BLK>(
         S, n, ts, W,
         [&](int j, TravState& st) {
-            const float4 a = ldq_x(W.sh_o + j), c = ldq_x(W.sh_d + j);
+            const float4 a = W.sh_o[j], c = W.sh_d[j];
             trav_init(st, mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), 0.0f, c.w);
             st.path = __float_as_int(a.w);
         },
@@ -1413,21 +1198,6 @@ __global__ __launch_bounds__(BLK, wf_waves(false)) void k_shadow_vis(DevScene S,
             const bool occluded = st.h.tri >= 0;
             W.vis[j] = table ? (occluded ? 0 : 1) : (occluded ? -1 : st.path);
         }, cnt(W, b, kPoolSh));
-}
-
-// PT_NEE_MODE 2: the unoccluded shadow rays of k_trace_pair(b) add their contributions to the
-// path radiance in shadow-queue order (sh_c[j] = contribution | path, or -1 when occluded).
-__global__ __launch_bounds__(kBlockWF) void k_nee_add(WFState W, int b) {
-    const int n = *cnt(W, b, kShadowQ);
-    if (wf_cancelled(W)) return;
-    for (int j = (int)(blockIdx.x * kBlockWF + threadIdx.x); j < n; j += (int)(gridDim.x * kBlockWF)) {
-        const float4 k = ldqs(W.sh_c + j);
-        const int p = __float_as_int(k.w);
-        if (p >= 0) {
-            const float4 l = W.L[p];
-            W.L[p] = make_float4(l.x + k.x, l.y + k.y, l.z + k.z, 0.0f);
-        }
-    }
 }
 
 // Visible shadow rays of bounce b -> the NEE bucket queues (vis[j] = item | bucket << 28, or -1).
@@ -1508,7 +1278,7 @@ __device__ __forceinline__ int nee_entry(const WFState& W, int b, int idx) {
 __device__ __forceinline__ int smp_entry(const WFState& W, int b, int idx) {
     int base = 0;
 #pragma unroll
-    for (int q = 0; q < kSmpBuckets; ++q) {
+    for (int q = 0; q < kShadeBuckets; ++q) {
         const int n = *cnt(W, b, kSmp0 + q);
         if (idx < base + n) return W.sq[smp_index(W, q, idx - base)];
         base += n;
@@ -1518,7 +1288,7 @@ __device__ __forceinline__ int smp_entry(const WFState& W, int b, int idx) {
 __device__ __forceinline__ int smp_total(const WFState& W, int b) {
     int n = 0;
 #pragma unroll
-    for (int q = 0; q < kSmpBuckets; ++q) n += *cnt(W, b, kSmp0 + q);
+    for (int q = 0; q < kShadeBuckets; ++q) n += *cnt(W, b, kSmp0 + q);
     return n;
 }
 __device__ __forceinline__ int nee_total(const WFState& W, int b) {
@@ -1537,7 +1307,7 @@ __device__ __forceinline__ int nee_total(const WFState& W, int b) {
 template <int MODE, bool TEX>
 __global__ __launch_bounds__(kBlockShB, PT_SHB_WAVES) void k_shade_nee(DevScene S, DevLaunch L, WFState W, int b) {
     if (blockIdx.x == 0 && threadIdx.x == 0 && L.counters)
-        atomicAdd(&L.counters[15], (unsigned long long)nee_total(W, b));
+        atomicAdd(&L.counters[kCtrShadeItems], (unsigned long long)nee_total(W, b));
     if ((int)(blockIdx.x * kBlockShB) >= nee_total(W, b)) return;  // block-uniform
     if (wf_cancelled(W)) return;  // no barrier below
     const int j = nee_entry(W, b, (int)(blockIdx.x * kBlockShB + threadIdx.x));
@@ -1547,10 +1317,9 @@ __global__ __launch_bounds__(kBlockShB, PT_SHB_WAVES) void k_shade_nee(DevScene 
     const Hit h = decode_hit(hv);
     SurfaceHit sf;
     reconstruct<TEX>(S, h, mk(c.x, c.y, c.z), sf);
-#if PT_NEE_LEAN
     // only the path, the light index, |cos| and the squared distance stay live across the layered
     // walk; the throughput and the light are loaded again after it (the same values and
-    // operations as below, so the same bits)
+    // operations as loading them before it, so the same bits)
     const int aux = W.aux[path];
     const int li = aux >> 1;
     uint32_t seed = __float_as_uint(W.beta[path].w);
@@ -1564,24 +1333,6 @@ __global__ __launch_bounds__(kBlockShB, PT_SHB_WAVES) void k_shade_nee(DevScene 
         d2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
     }
     const float cosl = abs_dot(lds, mk(0.0f, 0.0f, 1.0f));
-#if PT_NEE_PROBE
-    // probe build only (tools/nee_probe.py): waves of the layered walk, those of them on its run-time
-    // path (some lane has the light across the shading plane) and those with both top kinds
-    if (L.counters) {
-        const bool lay = MODE == kModeLayered || !(aux & 1);
-        const unsigned long long any = __builtin_amdgcn_ballot_w64(lay);
-        const unsigned long long cross = __builtin_amdgcn_ballot_w64(lay && !same_hemisphere(sf.wo, lds));
-        const unsigned long long spec = __builtin_amdgcn_ballot_w64(lay && sqr(sf.roughness) < 1e-3f);
-        const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
-        if (lane_id() == __ffsll((long long)act) - 1 && any) {
-            atomicAdd(&L.counters[21], 1ull);
-            if (cross) atomicAdd(&L.counters[20], 1ull);
-            if (spec && spec != any) atomicAdd(&L.counters[22], 1ull);
-            atomicAdd(&L.counters[23], (unsigned long long)__popcll(cross));
-            atomicAdd(&L.counters[24], (unsigned long long)__popcll(any));
-        }
-    }
-#endif
     f3 f = bsdf_f<MODE, true>(seed, sf.albedo, sf.roughness, aux & 1, sf.wo, lds);
     f3 spectrum = f * cosl;
     const float4 bv = W.beta[path];
@@ -1594,27 +1345,6 @@ __global__ __launch_bounds__(kBlockShB, PT_SHB_WAVES) void k_shade_nee(DevScene 
         float4 l = W.L[path];
         W.L[path] = make_float4(l.x + add.x, l.y + add.y, l.z + add.z, 0.0f);
     }
-#else
-    const float4 bv = W.beta[path];
-    uint32_t seed = __float_as_uint(bv.w);
-    const f3 beta = mk(bv.x, bv.y, bv.z);
-    const int aux = W.aux[path];
-    const int li = aux >> 1;
-    const float P = L.n_lights == 1 ? 1.0f : 1.0f / (float)L.n_lights;
-    const DevLight lt = L.lights[li];
-    f3 lpos = mk(lt.px, lt.py, lt.pz);
-    f3 lds = to_local(sf.fr, normalize(lpos - sf.pos));
-    f3 f = bsdf_f<MODE>(seed, sf.albedo, sf.roughness, aux & 1, sf.wo, lds);
-    f3 spectrum = f * abs_dot(lds, mk(0.0f, 0.0f, 1.0f));
-    if (!is_zero(spectrum)) {
-        f3 dd = sf.pos - lpos;
-        float d2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
-        f3 Li = mk(lt.cr, lt.cg, lt.cb) / d2;
-        f3 add = ((beta * spectrum) * Li) / (P * 1.0f);
-        float4 l = W.L[path];
-        W.L[path] = make_float4(l.x + add.x, l.y + add.y, l.z + add.z, 0.0f);
-    }
-#endif
     W.beta[path] = make_float4(bv.x, bv.y, bv.z, __uint_as_float(seed));  // f may draw
 }
 
@@ -1722,12 +1452,27 @@ dim3 occupancy_grid(K kernel, int cus, int block = kBlockTrace) {
     } else {
         per_cu = it->second;
     }
-// (2x / 4x oversubscribed trace grids with the two wavefront streams: Lambert +0.2 / +0.5 %,
-// Dielectric +1.7 / +1.4 %, Layered -0.4 %: noise-level)
-#ifndef PT_TRACE_OVERSUB
-#define PT_TRACE_OVERSUB 1
-#endif
-    return dim3((unsigned)(PT_TRACE_OVERSUB * per_cu * std::max(1, cus)));
+    // (2x / 4x oversubscribed trace grids with the two wavefront streams: Lambert +0.2 / +0.5 %,
+    // Dielectric +1.7 / +1.4 %, Layered -0.4 %: noise-level, not kept)
+    return dim3((unsigned)(per_cu * std::max(1, cus)));
+}
+
+// A run-time flag as a compile-time constant: f(std::true_type{}) or f(std::false_type{}).
+template <class F>
+auto with_flag(bool v, F f) {
+    return v ? f(std::true_type{}) : f(std::false_type{});
+}
+// The variant of a trace kernel for a launch: f(tex, stats, block) with std::bool_constant TEX and
+// STATS and std::integral_constant<int> kBlockTraceWide or kBlockTrace.
+template <class F>
+hipError_t trace_variant(bool tex, bool wide, bool stats, F f) {
+    return with_flag(tex, [&](auto tx) {
+        return with_flag(wide, [&](auto wd) {
+            return with_flag(stats, [&](auto st) {
+                return f(tx, st, std::integral_constant<int, wd() ? kBlockTraceWide : kBlockTrace>{});
+            });
+        });
+    });
 }
 
 // phase (Default / Layered): 0 = k_shade_a, 1 = k_shade_nee, 2 = k_shade_smp
@@ -1736,14 +1481,10 @@ hipError_t launch_shade_t(bool fused, const DevScene& S, const DevLaunch& L, con
                           hipStream_t stream, int phase, int vis0, int shade0) {
     if (fused) {
         if constexpr (MODE == kModeLambert || MODE == kModeConductor || MODE == kModeDielectric)
-        {
-            if (shade0)
-                hipLaunchKernelGGL((k_shade_fused<MODE, TEX, true>), item_grid(items, shf_block(MODE)), dim3(shf_block(MODE)), 0,
+            with_flag(shade0 != 0, [&](auto s0) {
+                hipLaunchKernelGGL((k_shade_fused<MODE, TEX, s0()>), item_grid(items, shf_block(MODE)), dim3(shf_block(MODE)), 0,
                                    stream, S, L, W, b, vis0);
-            else
-                hipLaunchKernelGGL((k_shade_fused<MODE, TEX, false>), item_grid(items, shf_block(MODE)), dim3(shf_block(MODE)), 0,
-                                   stream, S, L, W, b, vis0);
-        }
+            });
     } else if (phase == 0) {
         hipLaunchKernelGGL((k_shade_a<MODE, TEX>), item_grid(items, kBlockShA), dim3(kBlockShA), 0, stream, S, L, W, b,
                            vis0);
@@ -1760,19 +1501,18 @@ hipError_t launch_shade_t(bool fused, const DevScene& S, const DevLaunch& L, con
 template <int MODE>
 hipError_t launch_shade(bool fused, const DevScene& S, const DevLaunch& L, const WFState& W, int b, int items,
                         hipStream_t stream, int phase, int vis0, int shade0) {
-    return S.texinfo ? launch_shade_t<MODE, true>(fused, S, L, W, b, items, stream, phase, vis0, shade0)
-                     : launch_shade_t<MODE, false>(fused, S, L, W, b, items, stream, phase, vis0, shade0);
+    return with_flag(S.texinfo != nullptr, [&](auto tx) {
+        return launch_shade_t<MODE, tx()>(fused, S, L, W, b, items, stream, phase, vis0, shade0);
+    });
 }
 
 template <int MODE>
 hipError_t launch_shade0_pixel_t(const DevScene& S, const DevLaunch& L, const WFState& W, int nf, hipStream_t stream) {
     constexpr int block = shf_block(MODE);
     const dim3 grid = item_grid(L.width * L.height, block);
-    if (S.texinfo)
-        hipLaunchKernelGGL((k_shade0_pixel<MODE, true>), grid, dim3(block), 0, stream, S, L, W, nf);
-    else
-        hipLaunchKernelGGL((k_shade0_pixel<MODE, false>), grid, dim3(block), 0, stream, S, L, W,
-                           nf);
+    with_flag(S.texinfo != nullptr, [&](auto tx) {
+        hipLaunchKernelGGL((k_shade0_pixel<MODE, tx()>), grid, dim3(block), 0, stream, S, L, W, nf);
+    });
     return hipGetLastError();
 }
 hipError_t launch_shade0_pixel(int mode, const DevScene& S, const DevLaunch& L, const WFState& W, int nf,
@@ -1885,75 +1625,40 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
         ++stimed;
         return hipSuccess;
     };
-    // the untextured trace kernels of a one-stream call take the wide workgroups (kBlockTraceWide)
-    const bool wide = wide_trace && (!tex || PT_WIDE_TEX);
-#define PT_TRACE_LAUNCH(KERN, BLK, ...) \
-    hipLaunchKernelGGL((KERN), occupancy_grid(KERN, cus, BLK), dim3(BLK), 0, stream, __VA_ARGS__)
-    auto extend = [&](int b, int dup, int copies) -> hipError_t {
+    // as shade_timed, for the trace launches of the fused modes' bounces and k_extend
+    auto trace_timed = [&](auto launch) -> hipError_t {
         hipError_t r;
         if (trace_events && (r = hipEventRecord(trace_events[2 * timed], stream)) != hipSuccess) return r;
-        if (tex && wide && PT_WIDE_TEX) {
-            if (stats)
-                PT_TRACE_LAUNCH((k_extend<true, true, kBlockTraceWide>), kBlockTraceWide, S, W, b, dup, copies, L.counters);
-            else
-                PT_TRACE_LAUNCH((k_extend<false, true, kBlockTraceWide>), kBlockTraceWide, S, W, b, dup, copies, L.counters);
-        } else if (tex) {
-            if (stats)
-                PT_TRACE_LAUNCH((k_extend<true, true>), kBlockTrace, S, W, b, dup, copies, L.counters);
-            else
-                PT_TRACE_LAUNCH((k_extend<false, true>), kBlockTrace, S, W, b, dup, copies, L.counters);
-        } else if (wide) {
-            if (stats)
-                PT_TRACE_LAUNCH((k_extend<true, false, kBlockTraceWide>), kBlockTraceWide, S, W, b, dup, copies, L.counters);
-            else
-                PT_TRACE_LAUNCH((k_extend<false, false, kBlockTraceWide>), kBlockTraceWide, S, W, b, dup, copies, L.counters);
-        } else if (stats) {
-            PT_TRACE_LAUNCH((k_extend<true, false>), kBlockTrace, S, W, b, dup, copies, L.counters);
-        } else {
-            PT_TRACE_LAUNCH((k_extend<false, false>), kBlockTrace, S, W, b, dup, copies, L.counters);
-        }
+        if ((r = launch()) != hipSuccess) return r;
         if (trace_events && (r = hipEventRecord(trace_events[2 * timed + 1], stream)) != hipSuccess) return r;
         ++timed;
+        return hipSuccess;
+    };
+    // a trace kernel on exactly the workgroups that are resident at once; wide_trace: the trace
+    // kernels of a one-stream call take the wide workgroups (kBlockTraceWide)
+    auto trace_launch = [&](auto kernel, int block, auto... args) -> hipError_t {
+        hipLaunchKernelGGL(kernel, occupancy_grid(kernel, cus, block), dim3(block), 0, stream, args...);
         return hipGetLastError();
+    };
+    auto extend = [&](int b, int dup, int copies) -> hipError_t {
+        return trace_timed([&] {
+            return trace_variant(tex, wide_trace, stats, [&](auto tx, auto st, auto blk) {
+                return trace_launch(k_extend<st(), tx(), blk()>, blk(), S, W, b, dup, copies, L.counters);
+            });
+        });
     };
     auto pair = [&](int b) -> hipError_t {
-        hipError_t r;
-        if (trace_events && (r = hipEventRecord(trace_events[2 * timed], stream)) != hipSuccess) return r;
-        if (tex && wide && PT_WIDE_TEX) {
-            if (stats)
-                PT_TRACE_LAUNCH((k_trace_pair<true, true, kBlockTraceWide>), kBlockTraceWide, S, W, b, L.counters);
-            else
-                PT_TRACE_LAUNCH((k_trace_pair<false, true, kBlockTraceWide>), kBlockTraceWide, S, W, b, L.counters);
-        } else if (tex) {
-            if (stats)
-                PT_TRACE_LAUNCH((k_trace_pair<true, true>), kBlockTrace, S, W, b, L.counters);
-            else
-                PT_TRACE_LAUNCH((k_trace_pair<false, true>), kBlockTrace, S, W, b, L.counters);
-        } else if (wide) {
-            if (stats)
-                PT_TRACE_LAUNCH((k_trace_pair<true, false, kBlockTraceWide>), kBlockTraceWide, S, W, b, L.counters);
-            else
-                PT_TRACE_LAUNCH((k_trace_pair<false, false, kBlockTraceWide>), kBlockTraceWide, S, W, b, L.counters);
-        } else if (stats) {
-            PT_TRACE_LAUNCH((k_trace_pair<true, false>), kBlockTrace, S, W, b, L.counters);
-        } else {
-            PT_TRACE_LAUNCH((k_trace_pair<false, false>), kBlockTrace, S, W, b, L.counters);
-        }
-        if (trace_events && (r = hipEventRecord(trace_events[2 * timed + 1], stream)) != hipSuccess) return r;
-        ++timed;
-        if (PT_NEE_MODE == 2 && !PT_PROBE_NO_NEE_ADD)
-            hipLaunchKernelGGL(k_nee_add, dim3(8 * cus), dim3(kBlockWF), 0, stream, W, b);
-        return hipGetLastError();
+        return trace_timed([&] {
+            return trace_variant(tex, wide_trace, stats, [&](auto tx, auto st, auto blk) {
+                return trace_launch(k_trace_pair<st(), tx(), blk()>, blk(), S, W, b, L.counters);
+            });
+        });
     };
-    auto shadow_vis = [&](int b, int table) -> hipError_t {
-        if (tex && wide && PT_WIDE_TEX)
-            PT_TRACE_LAUNCH((k_shadow_vis<true, kBlockTraceWide>), kBlockTraceWide, S, W, b, table, L.counters);
-        else if (tex)
-            PT_TRACE_LAUNCH((k_shadow_vis<true>), kBlockTrace, S, W, b, table, L.counters);
-        else if (wide)
-            PT_TRACE_LAUNCH((k_shadow_vis<false, kBlockTraceWide>), kBlockTraceWide, S, W, b, table, L.counters);
-        else
-            PT_TRACE_LAUNCH((k_shadow_vis<false>), kBlockTrace, S, W, b, table, L.counters);
+    auto shadow_vis = [&](int b, int table) -> hipError_t {  // k_shadow_vis has no STATS variant
+        const hipError_t r = trace_variant(tex, wide_trace, false, [&](auto tx, auto, auto blk) {
+            return trace_launch(k_shadow_vis<tx(), blk()>, blk(), S, W, b, table, L.counters);
+        });
+        if (r != hipSuccess) return r;
         if (!table) hipLaunchKernelGGL(k_nee_compact, item_grid(P, kBlockSh * kCompactPer), dim3(kBlockSh), 0, stream, W, b);
         return hipGetLastError();
     };
@@ -1963,15 +1668,10 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
     const int vis0 = (primary_dedup && nf > 1 && L.n_lights >= 1 && L.n_lights <= nf) ? L.n_lights : 0;
     auto shadow0 = [&]() -> hipError_t {
         if (!vis0) return hipSuccess;
-        if (tex)
-            hipLaunchKernelGGL(k_shadow0_setup<true>, item_grid(P1 * vis0, kBlockWF), dim3(kBlockWF),
-                               0, stream, S, L,
-                               W);
-        else
-            hipLaunchKernelGGL(k_shadow0_setup<false>, item_grid(P1 * vis0, kBlockWF), dim3(kBlockWF),
-                               0, stream, S,
-                               L, W);
-        hipError_t r = hipGetLastError();
+        hipError_t r = with_flag(tex, [&](auto tx) {
+            hipLaunchKernelGGL(k_shadow0_setup<tx()>, item_grid(P1 * vis0, kBlockWF), dim3(kBlockWF), 0, stream, S, L, W);
+            return hipGetLastError();
+        });
         if (r != hipSuccess || (r = shadow_vis(0, 1)) != hipSuccess) return r;
         // the table's rays must not be traced again as bounce-0 shadow rays
         return hipMemsetAsync(W.count + kShadowQ * kCntStride, 0, sizeof(int), stream);
@@ -2013,7 +1713,6 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
                 return e;
         }
     }
-#undef PT_TRACE_LAUNCH
     if (accum_wait && (e = hipStreamWaitEvent(stream, accum_wait, 0)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_accum, item_grid(L.width * L.height, kBlockWF), dim3(kBlockWF), 0, stream, W, L, nf);
     if (accum_done && (e = hipEventRecord(accum_done, stream)) != hipSuccess) return e;

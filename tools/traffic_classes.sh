@@ -2,7 +2,8 @@
 # Where k_trace_pair's memory traffic goes: PMC passes over
 # tools/perf_probe.py (Lambert, 1080p, 64 frames per batch) for libptamd variants, one rocprofv3 run
 # per counter group, plus a traversal-statistics run for the per-launch ray counts.
-#   tools/traffic_classes.sh OUTDIR "base noadd ntq"    (SIZES_ONLY=1: the read-request size pass alone)
+#   tools/traffic_classes.sh OUTDIR "base NAME ..."    (NAME: a tools/build_variants.sh library;
+#   SIZES_ONLY=1: the read-request size pass alone)
 set -e
 OUT=${1:-gpurun_out/tc}; VARS=${2:-base}
 ROOT="$GRAFT_REPO_ROOT"; [ -z "$ROOT" ] && ROOT=$(pwd)
