@@ -218,6 +218,47 @@ class OptixRendererT {
         check(pt_get_denoise_info(r_, &i), "pt_get_denoise_info");
         return i;
     }
+    // --- temporal reprojection and the variance-guided filter (pt_denoise_temporal): Denoise with the
+    // previous call's result reprojected through the previous call's camera.
+    static pt_temporal_options TemporalDefaults() {
+        pt_temporal_options o;
+        o.struct_size = (uint32_t)sizeof o;
+        check(pt_temporal_options_default(&o), "pt_temporal_options_default");
+        return o;
+    }
+    // Filters the accumulated sum times `scale` into h_pixels (W*H vec3).
+    template <class Vec3>
+    void DenoiseTemporal(Vec3 h_pixels[], float scale, const pt_temporal_options* temporal = nullptr,
+                         const pt_denoise_options* options = nullptr) {
+        static_assert(sizeof(Vec3) == 3 * sizeof(float), "h_pixels must be glm::vec3-like");
+        check(pt_denoise_temporal(r_, PT_DENOISE_SRC_ACCUM, nullptr, scale, temporal, options,
+                                  reinterpret_cast<float*>(h_pixels)),
+              "pt_denoise_temporal");
+    }
+    // Filters a caller's image (W*H vec3) into h_pixels.
+    template <class Vec3>
+    void DenoiseTemporal(const Vec3 source[], Vec3 h_pixels[], const pt_temporal_options* temporal = nullptr,
+                         const pt_denoise_options* options = nullptr) {
+        static_assert(sizeof(Vec3) == 3 * sizeof(float), "h_pixels must be glm::vec3-like");
+        check(pt_denoise_temporal(r_, PT_DENOISE_SRC_HOST, reinterpret_cast<const float*>(source), 1.0f, temporal, options,
+                                  reinterpret_cast<float*>(h_pixels)),
+              "pt_denoise_temporal");
+    }
+    void TemporalReset() { check(pt_temporal_reset(r_), "pt_temporal_reset"); }
+    // State of the last DenoiseTemporal (PT_TEMPORAL_*): W*H*channels floats, row 0 = bottom.
+    std::vector<float> TemporalState(int kind) {
+        const int ch = pt_temporal_channels(kind);
+        if (ch < 0) throw std::runtime_error("TemporalState: no such kind");
+        std::vector<float> out((size_t)w_ * (size_t)h_ * (size_t)ch);
+        check(pt_temporal_download(r_, kind, out.data(), (int64_t)(out.size() * sizeof(float))), "pt_temporal_download");
+        return out;
+    }
+    pt_temporal_info TemporalInfo() {
+        pt_temporal_info i;
+        i.struct_size = (uint32_t)sizeof i;
+        check(pt_get_temporal_info(r_, &i), "pt_get_temporal_info");
+        return i;
+    }
     pt_renderer* handle() { return r_; }
 
    private:

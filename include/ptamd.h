@@ -568,6 +568,57 @@ typedef struct pt_denoise_info {
 /* Waits for the library stream. */
 int pt_get_denoise_info(pt_renderer* r, pt_denoise_info* out);
 
+/* ---- temporal reprojection and the variance-guided filter --------------------
+ * SVGF (Schied et al. 2017) on top of pt_denoise: a call reprojects the previous call's filtered
+ * colour, luminance moments and history length through the previous call's camera, accepts them
+ * per pixel where the previous guides show the same surface, blends this call's source into them,
+ * and runs the a-trous iterations with a colour term scaled by the estimated variance.  A camera
+ * or committed geometry change therefore keeps the samples of the surfaces still in view.  There
+ * are no motion vectors: a point on a moved mesh fails the plane test and starts again.  Same
+ * device, stream and ordering as pt_denoise. */
+typedef struct pt_temporal_options {
+    uint32_t struct_size;
+    float alpha;              /* (0, 1]: the share of the new colour; at least 1 / history length */
+    float alpha_moments;      /* (0, 1]: likewise for the luminance moments */
+    int32_t max_history;      /* >= 1: the history length stops growing here */
+    float normal_cos;         /* [-1, 1]: a tap is accepted if dot(n_prev, n) >= normal_cos */
+    float plane_distance;     /* > 0: ... and |dot(pos - pos_prev, n)| <= plane_distance * depth */
+    float sigma_luminance;    /* > 0: the colour term is |dl| / (sigma_luminance * sqrt(variance) + 1e-8) */
+    int32_t variance_history; /* >= 0: below this history length the variance is estimated spatially (7x7) */
+} pt_temporal_options;
+/* Fills the defaults (0.2, 0.2, 32, 0.9, 0.02, 4.0, 4) into the first o->struct_size bytes. */
+int pt_temporal_options_default(pt_temporal_options* o);
+/* As pt_denoise (sources, scale, NULL = defaults, host_out, asynchrony), with the history of the
+ * previous call; this call's view and filtered state become the history of the next.  dopt gives
+ * iterations, demodulate, sigma_normal, sigma_position and albedo_floor; its sigma_color is not
+ * used.  The result is where pt_denoised_device_ptr points.  PT_ERR_INVALID for what pt_denoise
+ * refuses and for a temporal option outside the range given above. */
+int pt_denoise_temporal(pt_renderer* r, int32_t source, const float* host_in, float scale, const pt_temporal_options* topt,
+                        const pt_denoise_options* dopt, float* host_out);
+/* Drops the history: the next call starts every pixel again.  pt_resize does the same. */
+int pt_temporal_reset(pt_renderer* r);
+#define PT_TEMPORAL_HISTORY_LENGTH 0 /* float x 1: 0 at a miss, 1 where the history was not accepted */
+#define PT_TEMPORAL_MOMENTS 1        /* float x 2: first and second moment of the luminance */
+#define PT_TEMPORAL_VARIANCE 2       /* float x 1: the variance that entered iteration 0 */
+#define PT_TEMPORAL_COLOR 3          /* float x 3: the stored colour history (iteration 0's result, demodulated) */
+/* Channels of a PT_TEMPORAL_* kind; -1 for an unknown kind. */
+int pt_temporal_channels(int32_t kind);
+/* Copies state of the last pt_denoise_temporal to host; bytes must be W * H * channels * 4.
+ * PT_ERR_STATE before the first call (or after a pt_resize). */
+int pt_temporal_download(pt_renderer* r, int32_t kind, void* host, int64_t bytes);
+typedef struct pt_temporal_info {
+    uint32_t struct_size;
+    int32_t history_valid;       /* != 0: the next call has a history to reproject into */
+    uint64_t calls;              /* pt_denoise_temporal calls since pt_create */
+    uint64_t reprojected_pixels; /* hit pixels of the last call with accepted history */
+    uint64_t reset_pixels;       /* hit pixels of the last call without */
+    double temporal_ms;          /* HIP-event times of the last call: pack, reproject and blend */
+    double variance_ms;          /* the spatial variance estimate */
+    double filter_ms;            /* the iterations with their divisor passes, and keeping the guides */
+} pt_temporal_info;
+/* Waits for the library stream. */
+int pt_get_temporal_info(pt_renderer* r, pt_temporal_info* out);
+
 /* ---- glTF scene loading -----------------------------------------
  * ModelLoader::LoadModel (ModelLoading/ModelLoader.cpp:10-244): glTF 2.0 (.gltf with external
  * or data-URI buffers, or .glb) -> an owned pt_scene for pt_create.  One mesh per triangle

@@ -192,6 +192,28 @@ class pt_denoise_info(C.Structure):
                 ("hit_pixels", C.c_uint64), ("gbuffer_ms", C.c_double), ("filter_ms", C.c_double)]
 
 
+PT_TEMPORAL_HISTORY_LENGTH, PT_TEMPORAL_MOMENTS, PT_TEMPORAL_VARIANCE, PT_TEMPORAL_COLOR = range(4)
+
+TEMPORAL_KINDS = {
+    "history_length": PT_TEMPORAL_HISTORY_LENGTH,
+    "moments": PT_TEMPORAL_MOMENTS,
+    "variance": PT_TEMPORAL_VARIANCE,
+    "color": PT_TEMPORAL_COLOR,
+}
+
+
+class pt_temporal_options(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("alpha", C.c_float), ("alpha_moments", C.c_float),
+                ("max_history", C.c_int32), ("normal_cos", C.c_float), ("plane_distance", C.c_float),
+                ("sigma_luminance", C.c_float), ("variance_history", C.c_int32)]
+
+
+class pt_temporal_info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("history_valid", C.c_int32), ("calls", C.c_uint64),
+                ("reprojected_pixels", C.c_uint64), ("reset_pixels", C.c_uint64), ("temporal_ms", C.c_double),
+                ("variance_ms", C.c_double), ("filter_ms", C.c_double)]
+
+
 class _pt_launch_frame(C.Structure):
     _fields_ = [("color_buffer", C.c_void_p), ("size", C.c_int32 * 2), ("id", C.c_uint32)]
 
@@ -281,6 +303,13 @@ SIGNATURES = {
     "pt_denoise": (C.c_int, [_R, C.c_int32, _FP, C.c_float, C.POINTER(pt_denoise_options), _FP]),
     "pt_denoised_device_ptr": (C.c_void_p, [_R]),
     "pt_get_denoise_info": (C.c_int, [_R, C.POINTER(pt_denoise_info)]),
+    "pt_temporal_options_default": (C.c_int, [C.POINTER(pt_temporal_options)]),
+    "pt_denoise_temporal": (C.c_int, [_R, C.c_int32, _FP, C.c_float, C.POINTER(pt_temporal_options),
+                                      C.POINTER(pt_denoise_options), _FP]),
+    "pt_temporal_reset": (C.c_int, [_R]),
+    "pt_temporal_channels": (C.c_int, [C.c_int32]),
+    "pt_temporal_download": (C.c_int, [_R, C.c_int32, C.c_void_p, C.c_int64]),
+    "pt_get_temporal_info": (C.c_int, [_R, C.POINTER(pt_temporal_info)]),
     "pt_model_load_gltf": (C.c_int, [C.c_char_p, pt_image_decode_fn, C.c_void_p, C.POINTER(_M)]),
     "pt_model_scene": (C.POINTER(pt_scene), [_M]),
     "pt_model_mesh_name": (C.c_char_p, [_M, C.c_int32]),

@@ -14,27 +14,13 @@
 // (measured: DESIGN.md §10).  The arithmetic is the specification in DESIGN.md §10, operation for
 // operation and the same in every variant (the build is -ffp-contract=off);
 // tests/test_gpu_denoise.py restates it in numpy and compares bit for bit.
-#include "pt_internal.h"
+#include "pt_atrous.h"
 
 namespace pt {
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kStack = PT_MK_STACK;
-constexpr int kTile = 16;  // pixels per workgroup side
-
-__device__ __forceinline__ void tile_pixel(int& x, int& y) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    x = blockIdx.x * kTile + (wave & 1) * 8 + (lane & 7);
-    y = blockIdx.y * kTile + (wave >> 1) * 8 + (lane >> 3);
-}
-
-__device__ __forceinline__ void store3(float* p, size_t i, f3 v) {
-    p[3 * i] = v.x;
-    p[3 * i + 1] = v.y;
-    p[3 * i + 2] = v.z;
-}
 
 template <bool TEX>
 __global__ __launch_bounds__(kBlock) void k_gbuffer(DevScene S, DevLaunch L, AovBuffers B) {
@@ -81,11 +67,6 @@ __global__ __launch_bounds__(kBlock) void k_gbuffer(DevScene S, DevLaunch L, Aov
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(B.hits, (unsigned long long)__popcll(m));
 }
 
-// a_p = max(albedo[p], floor) per channel
-__device__ __forceinline__ f3 albedo_floor(float4 a, float floor) {
-    return mk(a.x < floor ? floor : a.x, a.y < floor ? floor : a.y, a.z < floor ? floor : a.z);
-}
-
 // c_0: the source (W*H*3 floats, times scale) as 16-byte records, demodulated at the hit pixels.
 // The division runs here once per pixel, ahead of iteration 0's 25 loads of the record.
 __global__ __launch_bounds__(kBlock) void k_atrous_pack(const float* __restrict__ in, float scale, int demodulate,
@@ -103,11 +84,6 @@ __global__ __launch_bounds__(kBlock) void k_atrous_pack(const float* __restrict_
     c[p] = make_float4(v.x, v.y, v.z, 0.0f);
 }
 
-__device__ __forceinline__ float d2(float4 q, float4 p) {
-    const float x = q.x - p.x, y = q.y - p.y, z = q.z - p.z;
-    return (x * x + y * y) + z * z;
-}
-
 // One tap: q's records against the centre's.
 __device__ __forceinline__ void tap(float k, bool centre, float4 cq, float4 nq, float4 pq, float4 cp, float4 np,
                                     float4 pp, const AtrousParams& A, f3& acc, float& wsum) {
@@ -117,10 +93,6 @@ __device__ __forceinline__ void tap(float k, bool centre, float4 cq, float4 nq, 
     const float w = k * pt_expf_neg(-a);
     acc = mk(acc.x + cq.x * w, acc.y + cq.y * w, acc.z + cq.z * w);
     wsum += w;
-}
-
-__device__ __forceinline__ float b3(int i) {  // h = [1/16, 1/4, 3/8, 1/4, 1/16]
-    return i == 2 ? 0.375f : (i == 1 || i == 3) ? 0.25f : 0.0625f;
 }
 
 // c_{i+1}[p], or after the last iteration the remodulated result in the W*H*3 output.
@@ -249,8 +221,6 @@ __global__ __launch_bounds__(kBlock) void k_atrous_rows(AtrousParams A) {
     }
     atrous_store<LAST>(A, p, valid, out);
 }
-
-inline dim3 tile_grid(int w, int h) { return dim3((unsigned)((w + kTile - 1) / kTile), (unsigned)((h + kTile - 1) / kTile)); }
 
 }  // namespace
 

@@ -117,6 +117,45 @@ struct CreateGuard {
 
 }  // namespace
 
+namespace pt {
+
+// glm::inverse (detail/func_matrix.inl compute_inverse<4,4>) in fp32, operation for operation: the
+// inverses that pt_camera_from_blender hands out, and the ones pt_denoise_temporal takes of them.
+void mat4_inverse(const float* m, float* out) {
+    auto M = [&](int c, int r) { return m[c * 4 + r]; };
+    float C00 = M(2, 2) * M(3, 3) - M(3, 2) * M(2, 3), C02 = M(1, 2) * M(3, 3) - M(3, 2) * M(1, 3);
+    float C03 = M(1, 2) * M(2, 3) - M(2, 2) * M(1, 3), C04 = M(2, 1) * M(3, 3) - M(3, 1) * M(2, 3);
+    float C06 = M(1, 1) * M(3, 3) - M(3, 1) * M(1, 3), C07 = M(1, 1) * M(2, 3) - M(2, 1) * M(1, 3);
+    float C08 = M(2, 1) * M(3, 2) - M(3, 1) * M(2, 2), C10 = M(1, 1) * M(3, 2) - M(3, 1) * M(1, 2);
+    float C11 = M(1, 1) * M(2, 2) - M(2, 1) * M(1, 2), C12 = M(2, 0) * M(3, 3) - M(3, 0) * M(2, 3);
+    float C14 = M(1, 0) * M(3, 3) - M(3, 0) * M(1, 3), C15 = M(1, 0) * M(2, 3) - M(2, 0) * M(1, 3);
+    float C16 = M(2, 0) * M(3, 2) - M(3, 0) * M(2, 2), C18 = M(1, 0) * M(3, 2) - M(3, 0) * M(1, 2);
+    float C19 = M(1, 0) * M(2, 2) - M(2, 0) * M(1, 2), C20 = M(2, 0) * M(3, 1) - M(3, 0) * M(2, 1);
+    float C22 = M(1, 0) * M(3, 1) - M(3, 0) * M(1, 1), C23 = M(1, 0) * M(2, 1) - M(2, 0) * M(1, 1);
+    const float F0[4] = {C00, C00, C02, C03}, F1[4] = {C04, C04, C06, C07}, F2[4] = {C08, C08, C10, C11};
+    const float F3[4] = {C12, C12, C14, C15}, F4[4] = {C16, C16, C18, C19}, F5[4] = {C20, C20, C22, C23};
+    const float V0[4] = {M(1, 0), M(0, 0), M(0, 0), M(0, 0)}, V1[4] = {M(1, 1), M(0, 1), M(0, 1), M(0, 1)};
+    const float V2[4] = {M(1, 2), M(0, 2), M(0, 2), M(0, 2)}, V3[4] = {M(1, 3), M(0, 3), M(0, 3), M(0, 3)};
+    const float SA[4] = {+1, -1, +1, -1}, SB[4] = {-1, +1, -1, +1};
+    float I0[4], I1[4], I2[4], I3[4];
+    for (int i = 0; i < 4; ++i) {
+        I0[i] = (V1[i] * F0[i] - V2[i] * F1[i] + V3[i] * F2[i]) * SA[i];
+        I1[i] = (V0[i] * F0[i] - V2[i] * F3[i] + V3[i] * F4[i]) * SB[i];
+        I2[i] = (V0[i] * F1[i] - V1[i] * F3[i] + V3[i] * F5[i]) * SA[i];
+        I3[i] = (V0[i] * F2[i] - V1[i] * F4[i] + V2[i] * F5[i]) * SB[i];
+    }
+    float d0 = M(0, 0) * I0[0], d1 = M(0, 1) * I1[0], d2 = M(0, 2) * I2[0], d3 = M(0, 3) * I3[0];
+    float one = 1.0f / ((d0 + d1) + (d2 + d3));
+    for (int i = 0; i < 4; ++i) {
+        out[i] = I0[i] * one;
+        out[4 + i] = I1[i] * one;
+        out[8 + i] = I2[i] * one;
+        out[12 + i] = I3[i] * one;
+    }
+}
+
+}  // namespace pt
+
 extern "C" {
 
 const char* pt_last_error(void) { return g_last_error.c_str(); }
@@ -198,6 +237,7 @@ int pt_resize(pt_renderer* r, int32_t width, int32_t height) {
     r->d_accum.reset();
     r->d_display.reset();
     r->aov.release();
+    r->temporal.release();
     r->multi.d_part.reset();
     r->d_accum64.reset();
     r->multi.d_part64.reset();
@@ -695,44 +735,11 @@ int pt_camera_from_blender(const float bp[3], const float br[3], float fov_deg, 
     P[10] = -(zf + zn) / (zf - zn);
     P[11] = -1.0f;
     P[14] = -(2.0f * zf * zn) / (zf - zn);
-    // glm::inverse (detail/func_matrix.inl compute_inverse<4,4>)
-    auto inverse = [](const float* m, float* out) {
-        auto M = [&](int c, int r) { return m[c * 4 + r]; };
-        float C00 = M(2, 2) * M(3, 3) - M(3, 2) * M(2, 3), C02 = M(1, 2) * M(3, 3) - M(3, 2) * M(1, 3);
-        float C03 = M(1, 2) * M(2, 3) - M(2, 2) * M(1, 3), C04 = M(2, 1) * M(3, 3) - M(3, 1) * M(2, 3);
-        float C06 = M(1, 1) * M(3, 3) - M(3, 1) * M(1, 3), C07 = M(1, 1) * M(2, 3) - M(2, 1) * M(1, 3);
-        float C08 = M(2, 1) * M(3, 2) - M(3, 1) * M(2, 2), C10 = M(1, 1) * M(3, 2) - M(3, 1) * M(1, 2);
-        float C11 = M(1, 1) * M(2, 2) - M(2, 1) * M(1, 2), C12 = M(2, 0) * M(3, 3) - M(3, 0) * M(2, 3);
-        float C14 = M(1, 0) * M(3, 3) - M(3, 0) * M(1, 3), C15 = M(1, 0) * M(2, 3) - M(2, 0) * M(1, 3);
-        float C16 = M(2, 0) * M(3, 2) - M(3, 0) * M(2, 2), C18 = M(1, 0) * M(3, 2) - M(3, 0) * M(1, 2);
-        float C19 = M(1, 0) * M(2, 2) - M(2, 0) * M(1, 2), C20 = M(2, 0) * M(3, 1) - M(3, 0) * M(2, 1);
-        float C22 = M(1, 0) * M(3, 1) - M(3, 0) * M(1, 1), C23 = M(1, 0) * M(2, 1) - M(2, 0) * M(1, 1);
-        const float F0[4] = {C00, C00, C02, C03}, F1[4] = {C04, C04, C06, C07}, F2[4] = {C08, C08, C10, C11};
-        const float F3[4] = {C12, C12, C14, C15}, F4[4] = {C16, C16, C18, C19}, F5[4] = {C20, C20, C22, C23};
-        const float V0[4] = {M(1, 0), M(0, 0), M(0, 0), M(0, 0)}, V1[4] = {M(1, 1), M(0, 1), M(0, 1), M(0, 1)};
-        const float V2[4] = {M(1, 2), M(0, 2), M(0, 2), M(0, 2)}, V3[4] = {M(1, 3), M(0, 3), M(0, 3), M(0, 3)};
-        const float SA[4] = {+1, -1, +1, -1}, SB[4] = {-1, +1, -1, +1};
-        float I0[4], I1[4], I2[4], I3[4];
-        for (int i = 0; i < 4; ++i) {
-            I0[i] = (V1[i] * F0[i] - V2[i] * F1[i] + V3[i] * F2[i]) * SA[i];
-            I1[i] = (V0[i] * F0[i] - V2[i] * F3[i] + V3[i] * F4[i]) * SB[i];
-            I2[i] = (V0[i] * F1[i] - V1[i] * F3[i] + V3[i] * F5[i]) * SA[i];
-            I3[i] = (V0[i] * F2[i] - V1[i] * F4[i] + V2[i] * F5[i]) * SB[i];
-        }
-        float d0 = M(0, 0) * I0[0], d1 = M(0, 1) * I1[0], d2 = M(0, 2) * I2[0], d3 = M(0, 3) * I3[0];
-        float one = 1.0f / ((d0 + d1) + (d2 + d3));
-        for (int i = 0; i < 4; ++i) {
-            out[i] = I0[i] * one;
-            out[4 + i] = I1[i] * one;
-            out[8 + i] = I2[i] * one;
-            out[12 + i] = I3[i] * one;
-        }
-    };
     pos[0] = p.x;
     pos[1] = p.y;
     pos[2] = p.z;
-    inverse(V, inv_view);
-    inverse(P, inv_proj);
+    mat4_inverse(V, inv_view);
+    mat4_inverse(P, inv_proj);
     return PT_OK;
 }
 

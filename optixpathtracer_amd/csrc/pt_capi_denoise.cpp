@@ -11,12 +11,6 @@ constexpr int kAovChannels[kAovKinds] = {3, 3, 3, 3, 1, 1, 2};
 
 const pt_denoise_options kDefaults = {(uint32_t)sizeof(pt_denoise_options), 5, 1, 1.0f, 0.3f, 1.0f, 1e-3f};
 
-// The first min(struct_size, sizeof(T)) bytes of a versioned struct travel; 0 = the size field itself is cut off.
-template <class T>
-size_t versioned_bytes(const T* s) {
-    return s->struct_size < sizeof(uint32_t) ? 0 : std::min<size_t>(s->struct_size, sizeof(T));
-}
-
 void* aov_ptr(pt_renderer* r, int kind) {
     pt_renderer::Aov& A = r->aov;
     switch (kind) {

@@ -198,4 +198,29 @@ hipError_t atrous_pack(const float* in, float scale, bool demodulate, float floo
                        float4* c, size_t n, hipStream_t stream);
 hipError_t atrous_iteration(const AtrousParams& A, bool last, int lds_max_step, hipStream_t stream);
 
+// Temporal reprojection and the variance-guided filter (pt_temporal.hip).  Records
+// of 16 bytes throughout: colour | variance, and moment 1 | moment 2 | history length | 0.
+struct TemporalParams {
+    const float4* c;           // this call's packed colour (atrous_pack)
+    const float4 *gn, *gp;     // this view's guides
+    const float4 *pgn, *pgp;   // the previous call's guides
+    const float4 *hc, *hm;     // the previous call's colour and moment records
+    float4 *tc, *tm;           // out: blended colour | variance, and the moment record
+    unsigned long long* count; // [0] hit pixels with accepted history, [1] without; zeroed by the caller
+    int w, h, history;         // history = 0: no previous call to reproject into
+    float prev_view[16], prev_proj[16];  // inverses of the previous call's inv_view and inv_proj
+    float alpha, alpha_moments, max_history, normal_cos, plane_distance;
+};
+hipError_t temporal_blend(const TemporalParams& T, hipStream_t stream);
+// tc[p].w of the hit pixels whose history is shorter than variance_history: the 7x7 estimate from tm.
+hipError_t temporal_variance(const float4* gn, const float4* gp, const float4* tm, float4* tc, int w, int h, float inv_n,
+                             float inv_p, float variance_history, hipStream_t stream);
+// den[p] = sigma_luminance * sqrt(3x3 Gaussian of cin.w) + 1e-8: the colour term's divisor of one iteration.
+hipError_t temporal_luminance_scale(const float4* cin, const float4* gn, float* den, int w, int h, float sigma_luminance,
+                                    hipStream_t stream);
+// One variance-guided iteration: AtrousParams as for atrous_iteration (inv_c is not read), den from
+// temporal_luminance_scale, and hist = where the colour | variance result is stored besides (or NULL).
+hipError_t temporal_atrous_iteration(const AtrousParams& A, const float* den, float4* hist, bool last, int lds_max_step,
+                                     hipStream_t stream);
+
 }  // namespace pt

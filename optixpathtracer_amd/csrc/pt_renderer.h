@@ -1,6 +1,6 @@
 // pt_renderer.h — the renderer behind the C ABI (include/ptamd.h) and what the driver's translation
 // units share: pt_capi.cpp (entry points), pt_capi_bake.cpp, pt_capi_scene.cpp, pt_capi_launch.cpp,
-// pt_capi_ahead.cpp, pt_capi_tables.cpp, pt_capi_stats.cpp and pt_capi_denoise.cpp.  Not part of the public ABI.
+// pt_capi_ahead.cpp, pt_capi_tables.cpp, pt_capi_stats.cpp, pt_capi_denoise.cpp and pt_capi_temporal.cpp.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -372,6 +372,30 @@ struct pt_renderer {
         }
     } aov;
 
+    // temporal reprojection (pt_capi_temporal.cpp, pt_temporal.hip): what the last
+    // pt_denoise_temporal left for the next one -- its guides and camera, the colour | variance
+    // history (iteration 0's result), the moment records (two sets: a call reads one and writes
+    // the other) -- and what pt_temporal_download shows of that call.
+    struct Temporal {
+        pt::DevBuf<float4> d_pgn, d_pgp;  // the guides of the last call's view
+        pt::DevBuf<float4> d_hc;          // colour | variance history
+        pt::DevBuf<float4> d_m[2];        // moment 1 | moment 2 | length | 0; d_m[cur] is the last call's
+        pt::DevBuf<float4> d_tc;          // what entered iteration 0: blended colour | variance
+        pt::DevBuf<float> d_den;          // the colour term's divisor of one iteration
+        pt::DevBuf<unsigned long long> d_count;  // reprojected, reset
+        int cur = 0;
+        bool valid = false;  // d_pgn .. d_m[cur] hold a call's state
+        float inv_view[16] = {}, inv_proj[16] = {};  // of that call
+        uint64_t calls = 0;
+        pt::Event ev[4];  // pack + blend | variance | iterations
+        bool timed = false;
+        void release() {
+            for (pt::DevBuf<float4>* b : {&d_pgn, &d_pgp, &d_hc, &d_m[0], &d_m[1], &d_tc}) b->reset();
+            d_den.reset();
+            valid = timed = false;
+        }
+    } temporal;
+
     pt_renderer() = default;
     ~pt_renderer();  // the queue sets (wavefront_free); everything else releases itself
     pt::DevScene scene() const {
@@ -434,7 +458,16 @@ int occ_table_upload(pt_renderer* r, const int32_t* entries, int64_t bytes);
 // pt_capi_stats.cpp
 int collect_pending(pt_renderer* r);
 
+// The first min(struct_size, sizeof(T)) bytes of a versioned struct travel; 0 = the size field itself is cut off.
+template <class T>
+size_t versioned_bytes(const T* s) {
+    return s->struct_size < sizeof(uint32_t) ? 0 : std::min<size_t>(s->struct_size, sizeof(T));
+}
+
 // pt_capi_denoise.cpp
 int gbuffer_prepare(pt_renderer* r);
+
+// pt_capi.cpp
+void mat4_inverse(const float* m, float* out);
 
 }  // namespace pt

@@ -1,0 +1,396 @@
+// pt_temporal.hip — temporal reprojection and the variance-guided a-trous filter (SVGF, Schied et
+// al. 2017) on top of the G-buffer and the filter of pt_aov.hip.  DESIGN.md §11.
+//
+// k_temporal: one thread per pixel, 8x8 pixels per wave (tile_pixel).  A hit pixel's world position
+// goes through the previous call's view and projection, the four bilinear taps around the point it
+// lands on are tested against the previous guides, and the accepted history is blended with this
+// call's colour and luminance moments.  Two counters, one atomic per workgroup each; nothing else is atomic.
+// k_temporal_variance: where the history is shorter than variance_history, the variance comes from
+// the moments of a 7x7 window, staged in LDS with its halo of 3 (a workgroup none of whose pixels
+// needs it returns before staging).
+// k_temporal_lscale: per iteration, the 3x3 Gaussian of the variance as the colour term's divisor.
+// k_tatrous / k_tatrous_rows: the iterations of k_atrous / k_atrous_rows over colour | variance
+// records, with the luminance term in place of the colour distance, staged exactly as those are.
+// Every load is a 16-byte record except the divisor; the arithmetic is the specification of §11,
+// the same in every variant (-ffp-contract=off); tests/temporal_ref.py restates it in numpy.
+#include "pt_atrous.h"
+
+namespace pt {
+
+namespace {
+
+__device__ __forceinline__ float luminance(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+__device__ __forceinline__ float dot3(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ bool finite(float v) { return fabsf(v) <= 3.402823466e+38f; }
+
+__global__ __launch_bounds__(kBlock) void k_temporal(TemporalParams T) {
+    int x, y;
+    tile_pixel(x, y);
+    bool hit = false, accepted = false;
+    if (x < T.w && y < T.h) {
+        const size_t p = (size_t)y * (size_t)T.w + (size_t)x;
+        const float4 c = T.c[p], np = T.gn[p];
+        hit = np.w != 0.0f;
+        float4 tc = make_float4(c.x, c.y, c.z, 0.0f), tm = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (hit) {
+            const float4 pp = T.gp[p];
+            const float l = luminance(c);
+            f3 hcol = mk(0.0f, 0.0f, 0.0f);
+            float h1 = 0.0f, h2 = 0.0f, hlen = 0.0f;
+            if (T.history) {
+                const float P[4] = {pp.x, pp.y, pp.z, 1.0f};
+                float vw[4], clip[4];
+                mat4_mul_vec4(T.prev_view, P, vw);
+                mat4_mul_vec4(T.prev_proj, vw, clip);
+                if (clip[3] > 0.0f) {
+                    const float fx = ((clip[0] / clip[3]) * 0.5f + 0.5f) * (float)T.w - 0.5f;
+                    const float fy = ((clip[1] / clip[3]) * 0.5f + 0.5f) * (float)T.h - 0.5f;
+                    // outside this range no tap is inside the image (a NaN is outside)
+                    if (fx >= -1.0f && fx < (float)T.w && fy >= -1.0f && fy < (float)T.h) {
+                        const float ffx = floorf(fx), ffy = floorf(fy);
+                        const int ix = (int)ffx, iy = (int)ffy;
+                        const float tx = fx - ffx, ty = fy - ffy;
+                        const float lim = T.plane_distance * pp.w;
+                        float ws = 0.0f;
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                            for (int i = 0; i < 2; ++i) {
+                                const int qx = ix + i, qy = iy + j;
+                                if (qx < 0 || qx >= T.w || qy < 0 || qy >= T.h) continue;
+                                const size_t q = (size_t)qy * (size_t)T.w + (size_t)qx;
+                                const float4 nq = T.pgn[q];
+                                if (nq.w == 0.0f) continue;
+                                if (!(dot3(nq, np) >= T.normal_cos)) continue;
+                                const float4 pq = T.pgp[q];
+                                const float4 d = make_float4(pp.x - pq.x, pp.y - pq.y, pp.z - pq.z, 0.0f);
+                                if (!(fabsf(dot3(d, np)) <= lim)) continue;
+                                const float4 hc = T.hc[q], hm = T.hm[q];
+                                if (!(finite(hc.x) && finite(hc.y) && finite(hc.z) && finite(hm.x) && finite(hm.y) &&
+                                      finite(hm.z)))
+                                    continue;
+                                const float wgt = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
+                                ws += wgt;
+                                hcol = mk(hcol.x + hc.x * wgt, hcol.y + hc.y * wgt, hcol.z + hc.z * wgt);
+                                h1 += hm.x * wgt;
+                                h2 += hm.y * wgt;
+                                hlen += hm.z * wgt;
+                            }
+                        }
+                        if (ws >= 0.01f) {
+                            accepted = true;
+                            hcol = mk(hcol.x / ws, hcol.y / ws, hcol.z / ws);
+                            h1 = h1 / ws;
+                            h2 = h2 / ws;
+                            hlen = hlen / ws;
+                        }
+                    }
+                }
+            }
+            f3 t = mk(c.x, c.y, c.z);
+            float m1 = l, m2 = l * l, N = 1.0f;
+            if (accepted) {
+                N = hlen + 1.0f;
+                if (!(N < T.max_history)) N = T.max_history;
+                const float r = 1.0f / N;
+                const float a = T.alpha < r ? r : T.alpha, am = T.alpha_moments < r ? r : T.alpha_moments;
+                t = mk(hcol.x + (c.x - hcol.x) * a, hcol.y + (c.y - hcol.y) * a, hcol.z + (c.z - hcol.z) * a);
+                m1 = h1 + (l - h1) * am;
+                m2 = h2 + (l * l - h2) * am;
+            }
+            const float dv = m2 - m1 * m1;
+            tc = make_float4(t.x, t.y, t.z, dv > 0.0f ? dv : 0.0f);
+            tm = make_float4(m1, m2, N, 0.0f);
+        }
+        T.tc[p] = tc;
+        T.tm[p] = tm;
+    }
+    // the two counters: the waves' ballots meet in LDS, one atomic per counter and workgroup
+    __shared__ unsigned cnt[2 * (kBlock / 64)];
+    const unsigned long long ma = __ballot(hit && accepted), mr = __ballot(hit && !accepted);
+    if ((threadIdx.x & 63) == 0) {
+        cnt[2 * (threadIdx.x >> 6)] = (unsigned)__popcll(ma);
+        cnt[2 * (threadIdx.x >> 6) + 1] = (unsigned)__popcll(mr);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const unsigned c = (cnt[threadIdx.x] + cnt[2 + threadIdx.x]) + (cnt[4 + threadIdx.x] + cnt[6 + threadIdx.x]);
+        if (c) atomicAdd(T.count + threadIdx.x, (unsigned long long)c);
+    }
+}
+
+// The 7x7 estimate: 16x16 pixels and their halo of 3, 22^2 records of 48 B (23 KB) in LDS.
+__global__ __launch_bounds__(kBlock) void k_temporal_variance(const float4* __restrict__ gn, const float4* __restrict__ gp,
+                                                              const float4* __restrict__ tm, float4* __restrict__ tc, int w,
+                                                              int h, float inv_n, float inv_p, float vh) {
+    constexpr int side = kTile + 6;
+    __shared__ float4 sn[side * side], sp[side * side], sm[side * side];
+    int x, y;
+    tile_pixel(x, y);
+    const bool inside = x < w && y < h;
+    const size_t p = inside ? (size_t)y * (size_t)w + (size_t)x : 0;
+    bool need = false;
+    if (inside) need = gn[p].w != 0.0f && tm[p].z < vh;
+    if (!__syncthreads_or(need ? 1 : 0)) return;
+    const int ox = blockIdx.x * kTile - 3, oy = blockIdx.y * kTile - 3;
+    for (int i = threadIdx.x; i < side * side; i += kBlock) {
+        const int gx = ox + i % side, gy = oy + i / side;
+        float4 n = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q = n, m = n;  // n.w = 0: no tap outside the image
+        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
+            const size_t g = (size_t)gy * (size_t)w + (size_t)gx;
+            n = gn[g];
+            q = gp[g];
+            m = tm[g];
+        }
+        sn[i] = n;
+        sp[i] = q;
+        sm[i] = m;
+    }
+    __syncthreads();
+    if (!need) return;
+    const int lp = (y - oy) * side + (x - ox);
+    const float4 np = sn[lp], pp = sp[lp];
+    float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+    for (int dy = -3; dy <= 3; ++dy) {
+#pragma unroll
+        for (int dx = -3; dx <= 3; ++dx) {
+            const int lq = lp + dy * side + dx;
+            const float4 nq = sn[lq];
+            if (nq.w == 0.0f) continue;
+            float wgt = 1.0f;
+            if (dx != 0 || dy != 0) wgt = pt_expf_neg(-(d2(nq, np) * inv_n + d2(sp[lq], pp) * inv_p));
+            const float4 mq = sm[lq];
+            sw += wgt;
+            s1 += mq.x * wgt;
+            s2 += mq.y * wgt;
+        }
+    }
+    const float mu1 = s1 / sw, mu2 = s2 / sw;
+    const float dv = mu2 - mu1 * mu1;
+    reinterpret_cast<float*>(tc)[4 * p + 3] = (dv > 0.0f ? dv : 0.0f) * (vh / sm[lp].z);
+}
+
+__device__ __forceinline__ float g3(int i) { return i == 1 ? 0.5f : 0.25f; }  // [1/4, 1/2, 1/4]
+
+__global__ __launch_bounds__(kBlock) void k_temporal_lscale(const float4* __restrict__ cin, const float4* __restrict__ gn,
+                                                            float* __restrict__ den, int w, int h, float sigma_l) {
+    int x, y;
+    tile_pixel(x, y);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * (size_t)w + (size_t)x;
+    float out = 0.0f;
+    if (gn[p].w != 0.0f) {
+        float sum = 0.0f, ks = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int qx = x + dx, qy = y + dy;
+                if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
+                if (gn[q].w == 0.0f) continue;
+                const float k = g3(dy + 1) * g3(dx + 1);
+                sum += cin[q].w * k;
+                ks += k;
+            }
+        }
+        out = sigma_l * sqrtf(sum / ks) + 1e-8f;
+    }
+    den[p] = out;
+}
+
+struct TAtrousParams {
+    AtrousParams A;
+    const float* den;
+    float4* hist;
+};
+
+// One tap: q's records against the centre's; lp = luminance(cp), den = the centre's divisor.
+__device__ __forceinline__ void ttap(float k, bool centre, float4 cq, float4 nq, float4 pq, float lp, float den, float4 np,
+                                     float4 pp, const AtrousParams& A, f3& acc, float& vacc, float& wsum) {
+    float a = (fabsf(luminance(cq) - lp) / den + d2(nq, np) * A.inv_n) + d2(pq, pp) * A.inv_p;
+    if (centre) a = 0.0f;
+    if (a != a) return;
+    const float w = k * pt_expf_neg(-a);
+    acc = mk(acc.x + cq.x * w, acc.y + cq.y * w, acc.z + cq.z * w);
+    vacc += cq.w * (w * w);
+    wsum += w;
+}
+
+template <bool LAST>
+__device__ __forceinline__ void tatrous_store(const TAtrousParams& T, size_t p, bool valid, f3 out, float v) {
+    const AtrousParams& A = T.A;
+    if (T.hist) T.hist[p] = make_float4(out.x, out.y, out.z, v);
+    if (LAST) {
+        if (valid && A.demodulate) out = out * albedo_floor(A.ga[p], A.floor);
+        store3(A.out, p, out);
+    } else {
+        A.cout[p] = make_float4(out.x, out.y, out.z, v);
+    }
+}
+
+// k_atrous's tiling: LSTEP > 0 stages (16 + 4 LSTEP)^2 records of 48 B; LSTEP = 0 loads every tap.
+template <bool LAST, int LSTEP>
+__global__ __launch_bounds__(kBlock) void k_tatrous(TAtrousParams T) {
+    const AtrousParams& A = T.A;
+    constexpr bool LDS = LSTEP > 0;
+    constexpr int side = kTile + 4 * LSTEP, kRecords = LDS ? side * side : 1;
+    __shared__ float4 sc[kRecords], sn[kRecords], sp[kRecords];
+    int x, y;
+    tile_pixel(x, y);
+    const int s = LDS ? LSTEP : A.step;
+    const int ox = blockIdx.x * kTile - 2 * s, oy = blockIdx.y * kTile - 2 * s;
+    if (LDS) {
+        for (int i = threadIdx.x; i < side * side; i += kBlock) {
+            const int gx = ox + i % side, gy = oy + i / side;
+            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = c, p = c;  // n.w = 0: no tap outside the image
+            if (gx >= 0 && gx < A.w && gy >= 0 && gy < A.h) {
+                const size_t g = (size_t)gy * (size_t)A.w + (size_t)gx;
+                c = A.cin[g];
+                n = A.gn[g];
+                p = A.gp[g];
+            }
+            sc[i] = c;
+            sn[i] = n;
+            sp[i] = p;
+        }
+        __syncthreads();
+    }
+    if (x >= A.w || y >= A.h) return;
+    const size_t p = (size_t)y * (size_t)A.w + (size_t)x;
+    const int lp = LDS ? (y - oy) * side + (x - ox) : 0;
+    const float4 cp = LDS ? sc[lp] : A.cin[p], np = LDS ? sn[lp] : A.gn[p], pp = LDS ? sp[lp] : A.gp[p];
+    const bool valid = np.w != 0.0f;
+    f3 out = mk(cp.x, cp.y, cp.z);
+    float v = cp.w;
+    if (valid) {
+        const float den = T.den[p], lum = luminance(cp);
+        f3 acc = mk(0.0f, 0.0f, 0.0f);
+        float wsum = 0.0f, vacc = 0.0f;
+#pragma unroll
+        for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int qx = x + dx * s, qy = y + dy * s;
+                const float k = b3(dy + 2) * b3(dx + 2);
+                float4 cq, nq, pq;
+                if (LDS) {
+                    const int lq = (qy - oy) * side + (qx - ox);
+                    nq = sn[lq];
+                    if (nq.w == 0.0f) continue;
+                    cq = sc[lq];
+                    pq = sp[lq];
+                } else {
+                    if (qx < 0 || qx >= A.w || qy < 0 || qy >= A.h) continue;
+                    const size_t q = (size_t)qy * (size_t)A.w + (size_t)qx;
+                    nq = A.gn[q];
+                    if (nq.w == 0.0f) continue;
+                    cq = A.cin[q];
+                    pq = A.gp[q];
+                }
+                ttap(k, dx == 0 && dy == 0, cq, nq, pq, lum, den, np, pp, A, acc, vacc, wsum);
+            }
+        }
+        out = mk(acc.x / wsum, acc.y / wsum, acc.z / wsum);
+        v = vacc / (wsum * wsum);
+    }
+    tatrous_store<LAST>(T, p, valid, out, v);
+}
+
+// k_atrous_rows's tiling for the steps 8 and 16: 32 columns of 8 rows `STEP` apart, (32 + 4 STEP) x 12 records.
+template <bool LAST, int STEP>
+__global__ __launch_bounds__(kBlock) void k_tatrous_rows(TAtrousParams T) {
+    const AtrousParams& A = T.A;
+    constexpr int kCols = 32, kRows = 8, side = kCols + 4 * STEP, kRecords = side * (kRows + 4);
+    __shared__ float4 sc[kRecords], sn[kRecords], sp[kRecords];
+    const int ox = blockIdx.x * kCols - 2 * STEP;
+    const int y0 = ((int)blockIdx.y / STEP) * (kRows * STEP) + (int)blockIdx.y % STEP;  // tile row 0
+    for (int i = threadIdx.x; i < kRecords; i += kBlock) {
+        const int gx = ox + i % side, gy = y0 + (i / side - 2) * STEP;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = c, p = c;  // n.w = 0: no tap outside the image
+        if (gx >= 0 && gx < A.w && gy >= 0 && gy < A.h) {
+            const size_t g = (size_t)gy * (size_t)A.w + (size_t)gx;
+            c = A.cin[g];
+            n = A.gn[g];
+            p = A.gp[g];
+        }
+        sc[i] = c;
+        sn[i] = n;
+        sp[i] = p;
+    }
+    __syncthreads();
+    const int col = threadIdx.x % kCols, row = threadIdx.x / kCols;
+    const int x = blockIdx.x * kCols + col, y = y0 + row * STEP;
+    if (x >= A.w || y >= A.h) return;
+    const size_t p = (size_t)y * (size_t)A.w + (size_t)x;
+    const int lp = (row + 2) * side + (x - ox);
+    const float4 cp = sc[lp], np = sn[lp], pp = sp[lp];
+    const bool valid = np.w != 0.0f;
+    f3 out = mk(cp.x, cp.y, cp.z);
+    float v = cp.w;
+    if (valid) {
+        const float den = T.den[p], lum = luminance(cp);
+        f3 acc = mk(0.0f, 0.0f, 0.0f);
+        float wsum = 0.0f, vacc = 0.0f;
+#pragma unroll
+        for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int lq = lp + dy * side + dx * STEP;
+                const float4 nq = sn[lq];
+                if (nq.w == 0.0f) continue;
+                ttap(b3(dy + 2) * b3(dx + 2), dx == 0 && dy == 0, sc[lq], nq, sp[lq], lum, den, np, pp, A, acc, vacc, wsum);
+            }
+        }
+        out = mk(acc.x / wsum, acc.y / wsum, acc.z / wsum);
+        v = vacc / (wsum * wsum);
+    }
+    tatrous_store<LAST>(T, p, valid, out, v);
+}
+
+template <bool LAST>
+hipError_t tatrous_launch(const TAtrousParams& T, int lds_max_step, hipStream_t stream) {
+    const AtrousParams& A = T.A;
+    const dim3 grid = tile_grid(A.w, A.h);
+    const int lstep = A.step <= std::min(lds_max_step, kAtrousLdsMaxStep) ? A.step : 0;
+    // k_tatrous_rows: 32 columns per workgroup; per band of 8 * step rows, one workgroup per row phase
+    const dim3 rows((unsigned)((A.w + 31) / 32), (unsigned)((A.h + 8 * A.step - 1) / (8 * A.step) * A.step));
+    switch (lstep) {
+        case 1: hipLaunchKernelGGL((k_tatrous<LAST, 1>), grid, dim3(kBlock), 0, stream, T); break;
+        case 2: hipLaunchKernelGGL((k_tatrous<LAST, 2>), grid, dim3(kBlock), 0, stream, T); break;
+        case 4: hipLaunchKernelGGL((k_tatrous<LAST, 4>), grid, dim3(kBlock), 0, stream, T); break;
+        case 8: hipLaunchKernelGGL((k_tatrous_rows<LAST, 8>), rows, dim3(kBlock), 0, stream, T); break;
+        case 16: hipLaunchKernelGGL((k_tatrous_rows<LAST, 16>), rows, dim3(kBlock), 0, stream, T); break;
+        default: hipLaunchKernelGGL((k_tatrous<LAST, 0>), grid, dim3(kBlock), 0, stream, T); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t temporal_blend(const TemporalParams& T, hipStream_t stream) {
+    hipLaunchKernelGGL(k_temporal, tile_grid(T.w, T.h), dim3(kBlock), 0, stream, T);
+    return hipGetLastError();
+}
+
+hipError_t temporal_variance(const float4* gn, const float4* gp, const float4* tm, float4* tc, int w, int h, float inv_n,
+                             float inv_p, float variance_history, hipStream_t stream) {
+    hipLaunchKernelGGL(k_temporal_variance, tile_grid(w, h), dim3(kBlock), 0, stream, gn, gp, tm, tc, w, h, inv_n, inv_p,
+                       variance_history);
+    return hipGetLastError();
+}
+
+hipError_t temporal_luminance_scale(const float4* cin, const float4* gn, float* den, int w, int h, float sigma_luminance,
+                                    hipStream_t stream) {
+    hipLaunchKernelGGL(k_temporal_lscale, tile_grid(w, h), dim3(kBlock), 0, stream, cin, gn, den, w, h, sigma_luminance);
+    return hipGetLastError();
+}
+
+hipError_t temporal_atrous_iteration(const AtrousParams& A, const float* den, float4* hist, bool last, int lds_max_step,
+                                     hipStream_t stream) {
+    const TAtrousParams T = {A, den, hist};
+    return last ? tatrous_launch<true>(T, lds_max_step, stream) : tatrous_launch<false>(T, lds_max_step, stream);
+}
+
+}  // namespace pt

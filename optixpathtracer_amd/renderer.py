@@ -323,6 +323,67 @@ class OptixRenderer:
         check(self.lib.pt_get_denoise_info(self.h, C.byref(s)), "pt_get_denoise_info")
         return {k: getattr(s, k) for k, _ in capi.pt_denoise_info._fields_ if k != "struct_size"}
 
+    def denoise_temporal(self, source="accum", scale: float = 1.0, download: bool = True, **options):
+        """pt_denoise_temporal: denoise() with the previous call's filtered colour, luminance moments
+        and history length reprojected through the previous call's camera, and a colour term scaled
+        by the estimated variance.  options: fields of pt_temporal_options (alpha,
+        alpha_moments, max_history, normal_cos, plane_distance, sigma_luminance, variance_history)
+        or of pt_denoise_options (sigma_color is not used).  This call's view and state become the
+        history of the next one."""
+        t, o = capi.pt_temporal_options(), capi.pt_denoise_options()
+        t.struct_size, o.struct_size = C.sizeof(t), C.sizeof(o)
+        check(self.lib.pt_temporal_options_default(C.byref(t)), "pt_temporal_options_default")
+        check(self.lib.pt_denoise_options_default(C.byref(o)), "pt_denoise_options_default")
+        for k, v in options.items():
+            if k != "struct_size" and k in dict(capi.pt_temporal_options._fields_):
+                setattr(t, k, v)
+            elif k != "struct_size" and k in dict(capi.pt_denoise_options._fields_):
+                setattr(o, k, v)
+            else:
+                raise capi.PTError(f"denoise_temporal: no such option {k!r}", capi.PT_ERR_INVALID)
+        w, h = self.size
+        host = None
+        if isinstance(source, str):
+            srcs = {"accum": capi.PT_DENOISE_SRC_ACCUM, "display": capi.PT_DENOISE_SRC_DISPLAY}
+            if source not in srcs:
+                raise capi.PTError(f"denoise_temporal: source must be 'accum', 'display' or an array, not {source!r}",
+                                   capi.PT_ERR_INVALID)
+            src = srcs[source]
+        else:
+            host = _f32(source)
+            if host.size != w * h * 3:
+                raise capi.PTError("denoise_temporal: the source array must hold H * W * 3 floats", capi.PT_ERR_INVALID)
+            src = capi.PT_DENOISE_SRC_HOST
+        out = np.empty((h, w, 3), np.float32) if download else None
+        check(self.lib.pt_denoise_temporal(self.h, src, fptr(host) if host is not None else None, float(scale),
+                                           C.byref(t), C.byref(o), fptr(out) if download else None), "pt_denoise_temporal")
+        return out
+
+    def temporal_reset(self) -> None:
+        """pt_temporal_reset: the next denoise_temporal() starts every pixel again."""
+        check(self.lib.pt_temporal_reset(self.h), "pt_temporal_reset")
+
+    def temporal_state(self, kind) -> np.ndarray:
+        """pt_temporal_download: state of the last denoise_temporal(), by name (capi.TEMPORAL_KINDS)
+        or PT_TEMPORAL_* value: (H, W) for history_length and variance, (H, W, 2) moments, (H, W, 3)
+        color."""
+        k = capi.TEMPORAL_KINDS[kind] if isinstance(kind, str) else int(kind)
+        ch = int(self.lib.pt_temporal_channels(k))
+        if ch < 0:
+            raise capi.PTError(f"temporal_state: no such kind {kind!r}", capi.PT_ERR_INVALID)
+        w, h = self.size
+        out = np.empty((h, w) if ch == 1 else (h, w, ch), np.float32)
+        check(self.lib.pt_temporal_download(self.h, k, out.ctypes.data, out.nbytes), "pt_temporal_download")
+        return out
+
+    def temporal_info(self) -> dict:
+        """pt_get_temporal_info: calls, history_valid, and of the last denoise_temporal() the
+        reprojected and reset hit pixels and the device times of its three stages."""
+        s = capi.pt_temporal_info()
+        s.struct_size = C.sizeof(s)
+        check(self.lib.pt_get_temporal_info(self.h, C.byref(s)), "pt_get_temporal_info")
+        return {k: getattr(s, k) for k, _ in capi.pt_temporal_info._fields_ if k != "struct_size"}
+
     def accum_clear(self) -> None:
         check(self.lib.pt_accum_clear(self.h), "pt_accum_clear")
 

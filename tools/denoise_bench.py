@@ -17,10 +17,21 @@ after a warm-up call, with min and max):
   denoise_wall_ms       wall time of one pt_denoise from the accumulator at the defaults, left on
                         the device (then pt_synchronize) and downloaded to the host
   render_wall_ms        wall time of one one-frame pt_render in the same process, for scale
+  temporal              pt_denoise_temporal at the defaults: temporal_ms, variance_ms,
+                        filter_ms (pt_temporal_info) and the wall time of a call left on the device, for
+                        the first call after a reset, a call from the same view as the one before (the
+                        fifth in a row: every history is past variance_history), and a call after a
+                        camera nudge; beside them pt_denoise's filter_ms, measured in the same rounds
+                        (each round: pt_denoise, reset + call, four static calls, nudge + call)
 
 No pass/fail bar.  The lines also go to `--out` (default profiles/denoise_bench.json).
 
+With `--ab-lib OTHER.so` a first line compares pt_denoise's filter_ms (sphere box, the defaults)
+between this build and another build of the library, e.g. the parent commit's: `--ab-rounds` rounds,
+in each a fresh process per build, one after the other on the same GPU.
+
   python tools/denoise_bench.py [--reps 9] [--iterations 5] [--size 1920x1080] [--out FILE]
+                                [--ab-lib OTHER.so] [--ab-rounds 3]
 """
 from __future__ import annotations
 
@@ -28,6 +39,7 @@ import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 from pathlib import Path
@@ -58,6 +70,74 @@ def filter_ms(r, lds: int, iterations: int) -> float:
     os.environ["PTAMD_DENOISE_LDS"] = str(lds)
     r.denoise("accum", 0.25, download=False, iterations=iterations)
     return r.denoise_info()["filter_ms"]
+
+
+def temporal_rows(r, sc, reps):
+    """The temporal filter's three cases and pt_denoise, alternating round by round."""
+    base = np.asarray(sc.camera_blender_pos, np.float32)
+    keys = ("temporal_ms", "variance_ms", "filter_ms")
+    rows = {c: {k: [] for k in keys + ("wall_ms",)} for c in ("after_reset", "static", "after_nudge")}
+    spatial, counts = [], {}
+
+    def call(case, keep):
+        wall = wall_ms(lambda: (r.denoise_temporal("accum", 0.25, download=False), r.synchronize()))
+        info = r.temporal_info()
+        if keep:
+            for k in keys:
+                rows[case][k].append(info[k])
+            rows[case]["wall_ms"].append(wall)
+            counts[case] = {"reprojected_pixels": info["reprojected_pixels"], "reset_pixels": info["reset_pixels"]}
+
+    for k in range(reps + 1):
+        r.denoise("accum", 0.25, download=False)
+        if k:
+            spatial.append(r.denoise_info()["filter_ms"])
+        r.temporal_reset()
+        call("after_reset", k)
+        for j in range(4):
+            call("static", k and j == 3)
+        r.SetCameraBlender(base + np.float32([1e-3 * (1 - k % 2), 0.0, 0.0]), sc.camera_blender_rot, sc.fov_deg)
+        call("after_nudge", k)
+    out = {c: {k: spread(v) for k, v in rows[c].items()} | counts[c] for c in rows}
+    out["denoise_filter_ms"] = spread(spatial)
+    return out
+
+
+def filter_only(w, h, depth, reps):
+    """One process of the A/B: pt_denoise's filter_ms at the defaults on the sphere box."""
+    r = setup_renderer(scenes.sphere_in_box("diffuse"), w, h, depth)
+    r.accum_clear()
+    r.render_frames(1, 4)
+    ms = []
+    for _ in range(reps + 1):
+        r.denoise("accum", 0.25, download=False)
+        ms.append(r.denoise_info()["filter_ms"])
+    r.close()
+    print(json.dumps(spread(ms[1:])), flush=True)
+
+
+def ab(other, a):
+    """pt_denoise's filter_ms of this build (a) against `other` (b), a fresh process each, alternating."""
+    cmd = [sys.executable, str(Path(__file__).resolve()), "--filter-only", "--size", a.size, "--reps", str(a.reps),
+           "--depth", str(a.depth)]
+    res = {"a": [], "b": []}
+    for _ in range(a.ab_rounds):
+        for side in ("a", "b"):
+            env = dict(os.environ)
+            env.pop("PTAMD_LIB", None)
+            if side == "b":
+                env["PTAMD_LIB"] = str(other)
+            p = subprocess.run(cmd, env=env, capture_output=True, text=True, check=True)
+            res[side].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    out = {"ab": "pt_denoise filter_ms, sphere_box_diffuse, defaults", "size": a.size, "reps": a.reps, "rounds": a.ab_rounds,
+           "a": "this build", "b": Path(other).name + " (the other build)"}
+    for side in ("a", "b"):
+        out[f"{side}_rounds"] = res[side]
+        out[f"{side}_median_of_medians"] = statistics.median(x["median"] for x in res[side])
+    out["a_over_b"] = out["a_median_of_medians"] / out["b_median_of_medians"]
+    line = json.dumps(out)
+    print(line, flush=True)
+    return line
 
 
 def run(name, sc, w, h, depth, reps, iterations):
@@ -109,6 +189,8 @@ def run(name, sc, w, h, depth, reps, iterations):
     out["denoise_wall_ms"] = {"device": spread(dev[1:]), "downloaded": spread(host[1:])}
     out["filter_ms_default"] = r.denoise_info()["filter_ms"]
 
+    out["temporal"] = temporal_rows(r, sc, reps)
+
     r.set_render_ahead(1)  # every call renders its own frame
     img = np.empty((h, w, 3), np.float32)
     rw = [wall_ms(lambda: r.Render(img)) for _ in range(reps + 1)]
@@ -126,10 +208,16 @@ def main():
     ap.add_argument("--size", default="1920x1080")
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "denoise_bench.json"))
+    ap.add_argument("--ab-lib", default=None, help="another build of libptamd.so to compare pt_denoise's filter_ms with")
+    ap.add_argument("--ab-rounds", type=int, default=3)
+    ap.add_argument("--filter-only", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     w, h = (int(x) for x in a.size.split("x"))
-    lines = [run("sphere_box_diffuse", scenes.sphere_in_box("diffuse"), w, h, a.depth, a.reps, a.iterations),
-             run("sponza_class", scenes.sponza_class(), w, h, a.depth, a.reps, a.iterations)]
+    if a.filter_only:
+        return filter_only(w, h, a.depth, a.reps)
+    head = [ab(a.ab_lib, a)] if a.ab_lib else []  # first: this process has not touched the GPU yet
+    lines = head + [run("sphere_box_diffuse", scenes.sphere_in_box("diffuse"), w, h, a.depth, a.reps, a.iterations),
+                    run("sponza_class", scenes.sponza_class(), w, h, a.depth, a.reps, a.iterations)]
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     Path(a.out).write_text("\n".join(lines) + "\n")
 
