@@ -253,6 +253,15 @@ class OptixRendererT {
         check(pt_temporal_download(r_, kind, out.data(), (int64_t)(out.size() * sizeof(float))), "pt_temporal_download");
         return out;
     }
+    // PT_MOTION_*: the G-buffer's barycentrics, or the previous positions / screen-space motion of the
+    // last DenoiseTemporal with motion_vectors on: W*H*channels floats, row 0 = bottom.
+    std::vector<float> Motion(int kind) {
+        const int ch = pt_motion_channels(kind);
+        if (ch < 0) throw std::runtime_error("Motion: no such kind");
+        std::vector<float> out((size_t)w_ * (size_t)h_ * (size_t)ch);
+        check(pt_motion_download(r_, kind, out.data(), (int64_t)(out.size() * sizeof(float))), "pt_motion_download");
+        return out;
+    }
     pt_temporal_info TemporalInfo() {
         pt_temporal_info i;
         i.struct_size = (uint32_t)sizeof i;

@@ -573,9 +573,9 @@ int pt_get_denoise_info(pt_renderer* r, pt_denoise_info* out);
  * colour, luminance moments and history length through the previous call's camera, accepts them
  * per pixel where the previous guides show the same surface, blends this call's source into them,
  * and runs the a-trous iterations with a colour term scaled by the estimated variance.  A camera
- * or committed geometry change therefore keeps the samples of the surfaces still in view.  There
- * are no motion vectors: a point on a moved mesh fails the plane test and starts again.  Same
- * device, stream and ordering as pt_denoise. */
+ * or committed geometry change therefore keeps the samples of the surfaces still in view.  By
+ * default a point on a moved mesh fails the plane test and starts again; with motion_vectors on it
+ * is followed to where it was (below).  Same device, stream and ordering as pt_denoise. */
 typedef struct pt_temporal_options {
     uint32_t struct_size;
     float alpha;              /* (0, 1]: the share of the new colour; at least 1 / history length */
@@ -585,8 +585,9 @@ typedef struct pt_temporal_options {
     float plane_distance;     /* > 0: ... and |dot(pos - pos_prev, n)| <= plane_distance * depth */
     float sigma_luminance;    /* > 0: the colour term is |dl| / (sigma_luminance * sqrt(variance) + 1e-8) */
     int32_t variance_history; /* >= 0: below this history length the variance is estimated spatially (7x7) */
+    int32_t motion_vectors;   /* != 0: reproject a hit point from where it was on its triangle at the previous call */
 } pt_temporal_options;
-/* Fills the defaults (0.2, 0.2, 32, 0.9, 0.02, 4.0, 4) into the first o->struct_size bytes. */
+/* Fills the defaults (0.2, 0.2, 32, 0.9, 0.02, 4.0, 4, 0) into the first o->struct_size bytes. */
 int pt_temporal_options_default(pt_temporal_options* o);
 /* As pt_denoise (sources, scale, NULL = defaults, host_out, asynchrony), with the history of the
  * previous call; this call's view and filtered state become the history of the next.  dopt gives
@@ -615,9 +616,35 @@ typedef struct pt_temporal_info {
     double temporal_ms;          /* HIP-event times of the last call: pack, reproject and blend */
     double variance_ms;          /* the spatial variance estimate */
     double filter_ms;            /* the iterations with their divisor passes, and keeping the guides */
+    uint64_t moved_pixels;       /* hit pixels of the last call whose previous position differs from the present one */
+    double snapshot_ms;          /* HIP-event time of the last call's vertex snapshot; 0 if none ran */
+    int32_t motion_used;         /* 1 iff the motion kernel ran in the last call */
+    int32_t reserved;
 } pt_temporal_info;
 /* Waits for the library stream. */
 int pt_get_temporal_info(pt_renderer* r, pt_temporal_info* out);
+
+/* Motion vectors.  With pt_temporal_options.motion_vectors != 0 a call ends by
+ * keeping the world-space vertices of every triangle (one copy kernel, only when the geometry was
+ * committed since the copy was made).  The next such call, if geometry was committed in between,
+ * reprojects each hit pixel from pp = its barycentrics applied to its triangle's kept vertices --
+ * where that point of the surface was -- instead of from its present position; pp goes through the
+ * previous camera and into the plane test, everything else is as without the option.  Rigid moves
+ * and vertex deformation alike; several commits between two calls are one move.  A call whose
+ * predecessor did not have the option on, or that has no history, runs as without it and keeps the
+ * vertices for the next.  Off by default: a surface's irradiance is anchored to the static lights,
+ * not to the surface, so history followed across a move that changes the lighting is stale (measured
+ * in DESIGN.md §11). */
+#define PT_MOTION_BARYCENTRIC 0   /* float x 2: u, v of the G-buffer in force (rendered if stale, as pt_aov_download) */
+#define PT_MOTION_PREV_POSITION 1 /* float x 3: pp of the last pt_denoise_temporal with motion_vectors on; where that
+                                     call ran the plain kernel, the position guide itself; 0 at a miss */
+#define PT_MOTION_SCREEN 2        /* float x 3: (fx - x, fy - y, 1) in pixels for a hit pixel of a call that had a history
+                                     and clip.w > 0, with fx, fy of §11 step 1 from pp; else (0, 0, 0) */
+/* Channels of a PT_MOTION_* kind (2, 3, 3); < 0 for a kind that does not exist. */
+int pt_motion_channels(int32_t kind);
+/* Copies one of them to host; bytes must be W * H * channels * 4.  Kinds 1 and 2: PT_ERR_STATE unless
+ * the last pt_denoise_temporal had motion_vectors on. */
+int pt_motion_download(pt_renderer* r, int32_t kind, void* host, int64_t bytes);
 
 /* ---- glTF scene loading -----------------------------------------
  * ModelLoader::LoadModel (ModelLoading/ModelLoader.cpp:10-244): glTF 2.0 (.gltf with external

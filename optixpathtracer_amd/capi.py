@@ -205,13 +205,23 @@ TEMPORAL_KINDS = {
 class pt_temporal_options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("alpha", C.c_float), ("alpha_moments", C.c_float),
                 ("max_history", C.c_int32), ("normal_cos", C.c_float), ("plane_distance", C.c_float),
-                ("sigma_luminance", C.c_float), ("variance_history", C.c_int32)]
+                ("sigma_luminance", C.c_float), ("variance_history", C.c_int32), ("motion_vectors", C.c_int32)]
 
 
 class pt_temporal_info(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("history_valid", C.c_int32), ("calls", C.c_uint64),
                 ("reprojected_pixels", C.c_uint64), ("reset_pixels", C.c_uint64), ("temporal_ms", C.c_double),
-                ("variance_ms", C.c_double), ("filter_ms", C.c_double)]
+                ("variance_ms", C.c_double), ("filter_ms", C.c_double), ("moved_pixels", C.c_uint64),
+                ("snapshot_ms", C.c_double), ("motion_used", C.c_int32), ("reserved", C.c_int32)]
+
+
+PT_MOTION_BARYCENTRIC, PT_MOTION_PREV_POSITION, PT_MOTION_SCREEN = range(3)
+
+MOTION_KINDS = {
+    "barycentric": PT_MOTION_BARYCENTRIC,
+    "prev_position": PT_MOTION_PREV_POSITION,
+    "screen": PT_MOTION_SCREEN,
+}
 
 
 class _pt_launch_frame(C.Structure):
@@ -310,6 +320,8 @@ SIGNATURES = {
     "pt_temporal_channels": (C.c_int, [C.c_int32]),
     "pt_temporal_download": (C.c_int, [_R, C.c_int32, C.c_void_p, C.c_int64]),
     "pt_get_temporal_info": (C.c_int, [_R, C.POINTER(pt_temporal_info)]),
+    "pt_motion_channels": (C.c_int, [C.c_int32]),
+    "pt_motion_download": (C.c_int, [_R, C.c_int32, C.c_void_p, C.c_int64]),
     "pt_model_load_gltf": (C.c_int, [C.c_char_p, pt_image_decode_fn, C.c_void_p, C.POINTER(_M)]),
     "pt_model_scene": (C.POINTER(pt_scene), [_M]),
     "pt_model_mesh_name": (C.c_char_p, [_M, C.c_int32]),

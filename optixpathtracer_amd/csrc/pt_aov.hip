@@ -5,7 +5,8 @@
 // pixels, each wave64 an 8x8 quadrant).  The pixel's unjittered camera ray is traced over the
 // radiance ray's interval with the same strict re-trace rule and alpha cut-out, and the hit is
 // reconstructed as the first bounce of a path reconstructs it: what it writes equals the debug
-// record of that bounce bit for bit.  No queues, no random numbers.
+// record of that bounce bit for bit; the hit's barycentrics and primitive go into a guide record of
+// their own for the motion vectors of pt_temporal.hip.  No queues, no random numbers.
 //
 // k_atrous / k_atrous_rows: one iteration of the filter, one thread per pixel, ping-pong float4
 // colour buffers, no atomics.  Every load is a 16-byte record: the colour and the two guide records
@@ -37,7 +38,7 @@ __global__ __launch_bounds__(kBlock) void k_gbuffer(DevScene S, DevLaunch L, Aov
         hit = traverse<false, false, kStack, TEX>(S, o, d, 0.0f, 100.0f, h, stack + threadIdx.x, kBlock, ts);
         const size_t p = (size_t)y * (size_t)L.width + (size_t)x;
         f3 albedo = mk(0.0f, 0.0f, 0.0f), n = albedo, ng = albedo, pos = albedo;
-        float depth = 0.0f, rough = 0.0f, metal = 0.0f;
+        float depth = 0.0f, rough = 0.0f, metal = 0.0f, bu = 0.0f, bv = 0.0f;
         int prim = -1;
         if (hit) {
             SurfaceHit sf;
@@ -49,6 +50,8 @@ __global__ __launch_bounds__(kBlock) void k_gbuffer(DevScene S, DevLaunch L, Aov
             depth = h.t;
             rough = sf.roughness;
             metal = sf.metallic;
+            bu = h.u;
+            bv = h.v;
             prim = __float_as_int(S.isect[3 * h.tri].w);
         }
         store3(B.albedo, p, albedo);
@@ -62,6 +65,7 @@ __global__ __launch_bounds__(kBlock) void k_gbuffer(DevScene S, DevLaunch L, Aov
         B.guide_n[p] = make_float4(n.x, n.y, n.z, hit ? 1.0f : 0.0f);
         B.guide_p[p] = make_float4(pos.x, pos.y, pos.z, depth);
         B.guide_a[p] = make_float4(albedo.x, albedo.y, albedo.z, 0.0f);
+        B.guide_b[p] = make_float4(bu, bv, __int_as_float(prim), 0.0f);
     }
     const unsigned long long m = __ballot(hit);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(B.hits, (unsigned long long)__popcll(m));

@@ -35,6 +35,7 @@ int alloc_gbuffer(pt_renderer* r, size_t n) {
     PT_HIP(A.d_prim.alloc(n), "hipMalloc G-buffer");
     PT_HIP(A.d_ga.alloc(n), "hipMalloc G-buffer");
     PT_HIP(A.d_gp.alloc(n), "hipMalloc G-buffer");
+    PT_HIP(A.d_gb.alloc(n), "hipMalloc G-buffer");
     if (!A.d_hits) PT_HIP(A.d_hits.alloc(1), "hipMalloc G-buffer");
     PT_HIP(A.d_gn.alloc(n), "hipMalloc G-buffer");  // last: its size says that all of them exist
     return PT_OK;
@@ -67,7 +68,7 @@ int gbuffer_prepare(pt_renderer* r) {
     std::memcpy(L.inv_proj, r->inv_proj, sizeof L.inv_proj);
     L.debug_pixel = -1;
     const AovBuffers B = {A.d_albedo, A.d_normal, A.d_gnormal, A.d_position, A.d_depth, A.d_rough_metal,
-                          A.d_prim,   A.d_gn,     A.d_gp,      A.d_ga,       A.d_hits};
+                          A.d_prim,   A.d_gn,     A.d_gp,      A.d_ga,       A.d_gb,  A.d_hits};
     PT_HIP(A.ev_g[0].ensure(), "hipEventCreate");
     PT_HIP(A.ev_g[1].ensure(), "hipEventCreate");
     PT_HIP(hipMemsetAsync(A.d_hits, 0, sizeof(unsigned long long), r->stream), "hipMemset hit count");

@@ -168,11 +168,12 @@ hipError_t display_blend(float* fb, const float* frame, size_t n, float w, bool 
 
 // First-hit feature buffers and the a-trous filter (pt_aov.hip).  AovBuffers: what k_gbuffer writes
 // per pixel (row 0 = bottom): the seven AOVs of ptamd.h PT_AOV_*, the filter's 16-byte guide records
-// (normal | 1 at a hit, 0 at a miss; position | depth; albedo | 0) and the count of hit pixels.
+// (normal | 1 at a hit, 0 at a miss; position | depth; albedo | 0; Hit.u | Hit.v | prim's bits | 0,
+// the weights of v1 and v2 at the hit and 0, 0 at a miss) and the count of hit pixels.
 struct AovBuffers {
     float *albedo, *normal, *gnormal, *position, *depth, *rough_metal;
     int* prim;
-    float4 *guide_n, *guide_p, *guide_a;
+    float4 *guide_n, *guide_p, *guide_a, *guide_b;
     unsigned long long* hits;  // one counter, zeroed by the caller
 };
 // L: width, height, row0, image_height and the camera are read, nothing else.
@@ -206,12 +207,25 @@ struct TemporalParams {
     const float4 *pgn, *pgp;   // the previous call's guides
     const float4 *hc, *hm;     // the previous call's colour and moment records
     float4 *tc, *tm;           // out: blended colour | variance, and the moment record
-    unsigned long long* count; // [0] hit pixels with accepted history, [1] without; zeroed by the caller
+    unsigned long long* count; // [0] hit pixels with accepted history, [1] without, [2] moved (motion
+                               // only); zeroed by the caller
     int w, h, history;         // history = 0: no previous call to reproject into
     float prev_view[16], prev_proj[16];  // inverses of the previous call's inv_view and inv_proj
     float alpha, alpha_moments, max_history, normal_cos, plane_distance;
+    // motion only: the barycentric guide records, the vertex snapshot (3 records per global
+    // triangle, `ntri` of them) and where each pixel's previous position goes (0 at a miss)
+    const float4 *gb, *snap;
+    float4* pp;
+    int ntri;
 };
-hipError_t temporal_blend(const TemporalParams& T, hipStream_t stream);
+// motion: a hit pixel is reprojected from the point its triangle's snapshot vertices give at the
+// hit's barycentrics (DESIGN.md §11 "Motion vectors") instead of from its present position.
+hipError_t temporal_blend(const TemporalParams& T, bool motion, hipStream_t stream);
+// snap[3 g .. 3 g + 2] = the world-space vertices of leaf-order triangle t, g = its global index (isect[3 t].w).
+hipError_t temporal_snapshot(const float4* isect, const float4* shade, int ntri, float4* snap, hipStream_t stream);
+// out[3 p ..] = (fx - x, fy - y, 1) of §11 step 1 for pp[p] where gn[p].w != 0, history and clip.w > 0; else 0, 0, 0.
+hipError_t temporal_motion_screen(const float4* pp, const float4* gn, const float* prev_view, const float* prev_proj,
+                                  int history, int w, int h, float* out, hipStream_t stream);
 // tc[p].w of the hit pixels whose history is shorter than variance_history: the 7x7 estimate from tm.
 hipError_t temporal_variance(const float4* gn, const float4* gp, const float4* tm, float4* tc, int w, int h, float inv_n,
                              float inv_p, float variance_history, hipStream_t stream);

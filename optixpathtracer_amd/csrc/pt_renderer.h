@@ -352,7 +352,7 @@ struct pt_renderer {
     struct Aov {
         pt::DevBuf<float> d_albedo, d_normal, d_gnormal, d_position, d_depth, d_rough_metal;
         pt::DevBuf<int> d_prim;
-        pt::DevBuf<float4> d_gn, d_gp, d_ga;  // guide records (pt_internal.h AovBuffers)
+        pt::DevBuf<float4> d_gn, d_gp, d_ga, d_gb;  // guide records (pt_internal.h AovBuffers)
         pt::DevBuf<unsigned long long> d_hits;
         pt::DevBuf<float4> d_c[2];
         pt::DevBuf<float> d_out, d_in;
@@ -366,7 +366,7 @@ struct pt_renderer {
             for (pt::DevBuf<float>* b :
                  {&d_albedo, &d_normal, &d_gnormal, &d_position, &d_depth, &d_rough_metal, &d_out, &d_in})
                 b->reset();
-            for (pt::DevBuf<float4>* b : {&d_gn, &d_gp, &d_ga, &d_c[0], &d_c[1]}) b->reset();
+            for (pt::DevBuf<float4>* b : {&d_gn, &d_gp, &d_ga, &d_gb, &d_c[0], &d_c[1]}) b->reset();
             d_prim.reset();
             rendered = g_timed = f_timed = false;
         }
@@ -382,17 +382,28 @@ struct pt_renderer {
         pt::DevBuf<float4> d_m[2];        // moment 1 | moment 2 | length | 0; d_m[cur] is the last call's
         pt::DevBuf<float4> d_tc;          // what entered iteration 0: blended colour | variance
         pt::DevBuf<float> d_den;          // the colour term's divisor of one iteration
-        pt::DevBuf<unsigned long long> d_count;  // reprojected, reset
+        pt::DevBuf<unsigned long long> d_count;  // reprojected, reset, moved
         int cur = 0;
         bool valid = false;  // d_pgn .. d_m[cur] hold a call's state
         float inv_view[16] = {}, inv_proj[16] = {};  // of that call
         uint64_t calls = 0;
         pt::Event ev[4];  // pack + blend | variance | iterations
         bool timed = false;
+        // motion vectors (pt_temporal_options.motion_vectors): the world-space vertices per global
+        // triangle as of geometry version snap_version; snap_prev = it shows the geometry of the last
+        // call, which had the option on.  d_pp: the previous positions the motion kernel wrote.
+        pt::DevBuf<float4> d_snap, d_pp;
+        uint32_t snap_version = 0;
+        bool snap_have = false, snap_prev = false;
+        bool mv_last = false, mv_used = false;  // the last call: the option was on; the motion kernel ran
+        bool had_history = false;               // ... and it had a history,
+        float prev_view[16] = {}, prev_proj[16] = {};  // which it reprojected through these
+        pt::Event ev_s[2];  // around the last call's snapshot
+        bool snap_timed = false;
         void release() {
-            for (pt::DevBuf<float4>* b : {&d_pgn, &d_pgp, &d_hc, &d_m[0], &d_m[1], &d_tc}) b->reset();
+            for (pt::DevBuf<float4>* b : {&d_pgn, &d_pgp, &d_hc, &d_m[0], &d_m[1], &d_tc, &d_snap, &d_pp}) b->reset();
             d_den.reset();
-            valid = timed = false;
+            valid = timed = snap_have = snap_prev = mv_last = mv_used = had_history = snap_timed = false;
         }
     } temporal;
 

@@ -5,6 +5,12 @@
 // goes through the previous call's view and projection, the four bilinear taps around the point it
 // lands on are tested against the previous guides, and the accepted history is blended with this
 // call's colour and luminance moments.  Two counters, one atomic per workgroup each; nothing else is atomic.
+// k_temporal<true> (motion vectors): the point that goes through the previous camera and into the
+// plane test is the hit's previous position instead, the pixel's barycentrics applied to its
+// triangle's vertices in k_snapshot's copy of the previous call's geometry: one more guide record
+// and three vertex records per hit pixel, one more store, a third counter (the pixels that moved).
+// k_snapshot: one thread per leaf-order triangle, three 16-byte copies to its global index's slot.
+// k_motion_screen: the reprojected point's offset from the pixel, on demand (pt_motion_download).
 // k_temporal_variance: where the history is shorter than variance_history, the variance comes from
 // the moments of a 7x7 window, staged in LDS with its halo of 3 (a workgroup none of whose pixels
 // needs it returns before staging).
@@ -23,22 +29,38 @@ __device__ __forceinline__ float luminance(float4 c) { return (0.2126f * c.x + 0
 __device__ __forceinline__ float dot3(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ bool finite(float v) { return fabsf(v) <= 3.402823466e+38f; }
 
+template <bool MOTION>
 __global__ __launch_bounds__(kBlock) void k_temporal(TemporalParams T) {
     int x, y;
     tile_pixel(x, y);
-    bool hit = false, accepted = false;
+    bool hit = false, accepted = false, moved = false;
     if (x < T.w && y < T.h) {
         const size_t p = (size_t)y * (size_t)T.w + (size_t)x;
         const float4 c = T.c[p], np = T.gn[p];
         hit = np.w != 0.0f;
         float4 tc = make_float4(c.x, c.y, c.z, 0.0f), tm = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float4 prev = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (hit) {
             const float4 pp = T.gp[p];
+            // rp: the point reprojected and plane-tested; reconstruct's expression for s.pos over the snapshot
+            f3 rp = mk(pp.x, pp.y, pp.z);
+            if (MOTION) {
+                const float4 b = T.gb[p];
+                const int g = __float_as_int(b.z);
+                if (g >= 0 && g < T.ntri) {
+                    const float4 v0 = T.snap[3 * (size_t)g], v1 = T.snap[3 * (size_t)g + 1], v2 = T.snap[3 * (size_t)g + 2];
+                    const float u = b.x, v = b.y;
+                    const float w = 1.0f - u - v;
+                    rp = mk(w * v0.x + u * v1.x + v * v2.x, w * v0.y + u * v1.y + v * v2.y, w * v0.z + u * v1.z + v * v2.z);
+                }
+                moved = rp.x != pp.x || rp.y != pp.y || rp.z != pp.z;
+                prev = make_float4(rp.x, rp.y, rp.z, 0.0f);
+            }
             const float l = luminance(c);
             f3 hcol = mk(0.0f, 0.0f, 0.0f);
             float h1 = 0.0f, h2 = 0.0f, hlen = 0.0f;
             if (T.history) {
-                const float P[4] = {pp.x, pp.y, pp.z, 1.0f};
+                const float P[4] = {rp.x, rp.y, rp.z, 1.0f};
                 float vw[4], clip[4];
                 mat4_mul_vec4(T.prev_view, P, vw);
                 mat4_mul_vec4(T.prev_proj, vw, clip);
@@ -63,7 +85,7 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalParams T) {
                                 if (nq.w == 0.0f) continue;
                                 if (!(dot3(nq, np) >= T.normal_cos)) continue;
                                 const float4 pq = T.pgp[q];
-                                const float4 d = make_float4(pp.x - pq.x, pp.y - pq.y, pp.z - pq.z, 0.0f);
+                                const float4 d = make_float4(rp.x - pq.x, rp.y - pq.y, rp.z - pq.z, 0.0f);
                                 if (!(fabsf(dot3(d, np)) <= lim)) continue;
                                 const float4 hc = T.hc[q], hm = T.hm[q];
                                 if (!(finite(hc.x) && finite(hc.y) && finite(hc.z) && finite(hm.x) && finite(hm.y) &&
@@ -104,19 +126,63 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalParams T) {
         }
         T.tc[p] = tc;
         T.tm[p] = tm;
+        if (MOTION) T.pp[p] = prev;
     }
-    // the two counters: the waves' ballots meet in LDS, one atomic per counter and workgroup
-    __shared__ unsigned cnt[2 * (kBlock / 64)];
+    // the counters (two, with motion three): the waves' ballots meet in LDS, one atomic per counter and workgroup
+    constexpr int kCnt = MOTION ? 3 : 2;
+    __shared__ unsigned cnt[kCnt * (kBlock / 64)];
     const unsigned long long ma = __ballot(hit && accepted), mr = __ballot(hit && !accepted);
     if ((threadIdx.x & 63) == 0) {
-        cnt[2 * (threadIdx.x >> 6)] = (unsigned)__popcll(ma);
-        cnt[2 * (threadIdx.x >> 6) + 1] = (unsigned)__popcll(mr);
+        cnt[kCnt * (threadIdx.x >> 6)] = (unsigned)__popcll(ma);
+        cnt[kCnt * (threadIdx.x >> 6) + 1] = (unsigned)__popcll(mr);
+    }
+    if (MOTION) {
+        const unsigned long long mm = __ballot(hit && moved);
+        if ((threadIdx.x & 63) == 0) cnt[kCnt * (threadIdx.x >> 6) + 2] = (unsigned)__popcll(mm);
     }
     __syncthreads();
-    if (threadIdx.x < 2) {
-        const unsigned c = (cnt[threadIdx.x] + cnt[2 + threadIdx.x]) + (cnt[4 + threadIdx.x] + cnt[6 + threadIdx.x]);
+    if (threadIdx.x < kCnt) {
+        const unsigned c = (cnt[threadIdx.x] + cnt[kCnt + threadIdx.x]) + (cnt[2 * kCnt + threadIdx.x] + cnt[3 * kCnt + threadIdx.x]);
         if (c) atomicAdd(T.count + threadIdx.x, (unsigned long long)c);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void k_snapshot(const float4* __restrict__ isect, const float4* __restrict__ shade,
+                                                     int ntri, float4* __restrict__ snap) {
+    const int t = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (t >= ntri) return;
+    const float4 a = isect[3 * (size_t)t];
+    const int g = __float_as_int(a.w);
+    if (g < 0 || g >= ntri) return;
+    snap[3 * (size_t)g] = a;
+    snap[3 * (size_t)g + 1] = shade[4 * (size_t)t];
+    snap[3 * (size_t)g + 2] = shade[4 * (size_t)t + 1];
+}
+
+struct ScreenParams {
+    float prev_view[16], prev_proj[16];
+};
+
+__global__ __launch_bounds__(kBlock) void k_motion_screen(const float4* __restrict__ pp, const float4* __restrict__ gn,
+                                                          ScreenParams M, int history, int w, int h, float* __restrict__ out) {
+    int x, y;
+    tile_pixel(x, y);
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * (size_t)w + (size_t)x;
+    f3 o = mk(0.0f, 0.0f, 0.0f);
+    if (history && gn[p].w != 0.0f) {
+        const float4 q = pp[p];
+        const float P[4] = {q.x, q.y, q.z, 1.0f};
+        float vw[4], clip[4];
+        mat4_mul_vec4(M.prev_view, P, vw);
+        mat4_mul_vec4(M.prev_proj, vw, clip);
+        if (clip[3] > 0.0f) {
+            const float fx = ((clip[0] / clip[3]) * 0.5f + 0.5f) * (float)w - 0.5f;
+            const float fy = ((clip[1] / clip[3]) * 0.5f + 0.5f) * (float)h - 0.5f;
+            o = mk(fx - (float)x, fy - (float)y, 1.0f);
+        }
+    }
+    store3(out, p, o);
 }
 
 // The 7x7 estimate: 16x16 pixels and their halo of 3, 22^2 records of 48 B (23 KB) in LDS.
@@ -369,8 +435,26 @@ hipError_t tatrous_launch(const TAtrousParams& T, int lds_max_step, hipStream_t 
 
 }  // namespace
 
-hipError_t temporal_blend(const TemporalParams& T, hipStream_t stream) {
-    hipLaunchKernelGGL(k_temporal, tile_grid(T.w, T.h), dim3(kBlock), 0, stream, T);
+hipError_t temporal_blend(const TemporalParams& T, bool motion, hipStream_t stream) {
+    if (motion)
+        hipLaunchKernelGGL(k_temporal<true>, tile_grid(T.w, T.h), dim3(kBlock), 0, stream, T);
+    else
+        hipLaunchKernelGGL(k_temporal<false>, tile_grid(T.w, T.h), dim3(kBlock), 0, stream, T);
+    return hipGetLastError();
+}
+
+hipError_t temporal_snapshot(const float4* isect, const float4* shade, int ntri, float4* snap, hipStream_t stream) {
+    if (ntri <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_snapshot, dim3((unsigned)((ntri + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, isect, shade, ntri,
+                       snap);
+    return hipGetLastError();
+}
+
+hipError_t temporal_motion_screen(const float4* pp, const float4* gn, const float* prev_view, const float* prev_proj,
+                                  int history, int w, int h, float* out, hipStream_t stream) {
+    ScreenParams M;
+    for (int i = 0; i < 16; ++i) M.prev_view[i] = prev_view[i], M.prev_proj[i] = prev_proj[i];
+    hipLaunchKernelGGL(k_motion_screen, tile_grid(w, h), dim3(kBlock), 0, stream, pp, gn, M, history, w, h, out);
     return hipGetLastError();
 }
 

@@ -327,9 +327,9 @@ class OptixRenderer:
         """pt_denoise_temporal: denoise() with the previous call's filtered colour, luminance moments
         and history length reprojected through the previous call's camera, and a colour term scaled
         by the estimated variance.  options: fields of pt_temporal_options (alpha,
-        alpha_moments, max_history, normal_cos, plane_distance, sigma_luminance, variance_history)
-        or of pt_denoise_options (sigma_color is not used).  This call's view and state become the
-        history of the next one."""
+        alpha_moments, max_history, normal_cos, plane_distance, sigma_luminance, variance_history,
+        motion_vectors) or of pt_denoise_options (sigma_color is not used).  This call's view and state
+        become the history of the next one."""
         t, o = capi.pt_temporal_options(), capi.pt_denoise_options()
         t.struct_size, o.struct_size = C.sizeof(t), C.sizeof(o)
         check(self.lib.pt_temporal_options_default(C.byref(t)), "pt_temporal_options_default")
@@ -376,9 +376,23 @@ class OptixRenderer:
         check(self.lib.pt_temporal_download(self.h, k, out.ctypes.data, out.nbytes), "pt_temporal_download")
         return out
 
+    def motion(self, kind) -> np.ndarray:
+        """pt_motion_download, by name (capi.MOTION_KINDS) or PT_MOTION_* value: (H, W, 2) barycentric
+        (u, v of the G-buffer in force), and of the last denoise_temporal(motion_vectors=1) the
+        (H, W, 3) prev_position and screen (the reprojected point's offset in pixels | 1)."""
+        k = capi.MOTION_KINDS[kind] if isinstance(kind, str) else int(kind)
+        ch = int(self.lib.pt_motion_channels(k))
+        if ch < 0:
+            raise capi.PTError(f"motion: no such kind {kind!r}", capi.PT_ERR_INVALID)
+        w, h = self.size
+        out = np.empty((h, w, ch), np.float32)
+        check(self.lib.pt_motion_download(self.h, k, out.ctypes.data, out.nbytes), "pt_motion_download")
+        return out
+
     def temporal_info(self) -> dict:
         """pt_get_temporal_info: calls, history_valid, and of the last denoise_temporal() the
-        reprojected and reset hit pixels and the device times of its three stages."""
+        reprojected, reset and moved hit pixels, whether the motion kernel ran, and the device times
+        of its three stages and of its vertex snapshot."""
         s = capi.pt_temporal_info()
         s.struct_size = C.sizeof(s)
         check(self.lib.pt_get_temporal_info(self.h, C.byref(s)), "pt_get_temporal_info")

@@ -23,12 +23,20 @@ after a warm-up call, with min and max):
                         fifth in a row: every history is past variance_history), and a call after a
                         camera nudge; beside them pt_denoise's filter_ms, measured in the same rounds
                         (each round: pt_denoise, reset + call, four static calls, nudge + call)
+  motion                motion vectors (pt_temporal_options.motion_vectors): a call after a committed
+                        move of mesh 0 with the option on and with it off -- temporal_ms, the wall time
+                        of the call left on the device (with the G-buffer render the commit causes),
+                        moved_pixels, and for the option on snapshot_ms, the copy of the scene's
+                        vertices that ends the call (each round, per setting: reset, two static calls,
+                        move + commit + call; the settings alternate)
 
 No pass/fail bar.  The lines also go to `--out` (default profiles/denoise_bench.json).
 
-With `--ab-lib OTHER.so` a first line compares pt_denoise's filter_ms (sphere box, the defaults)
-between this build and another build of the library, e.g. the parent commit's: `--ab-rounds` rounds,
-in each a fresh process per build, one after the other on the same GPU.
+With `--ab-lib OTHER.so` a first line compares pt_denoise's filter_ms, the G-buffer's gbuffer_ms and
+the device time of a static pt_denoise_temporal call (temporal_ms + variance_ms + filter_ms, the
+options at their defaults) on the sphere box between this build and another build of the library,
+e.g. the parent commit's: `--ab-rounds` rounds, in each a fresh process per build, one after the
+other on the same GPU.
 
   python tools/denoise_bench.py [--reps 9] [--iterations 5] [--size 1920x1080] [--out FILE]
                                 [--ab-lib OTHER.so] [--ab-rounds 3]
@@ -103,17 +111,56 @@ def temporal_rows(r, sc, reps):
     return out
 
 
+def motion_rows(r, reps):
+    """A call after a committed mesh move, with motion vectors on and off, alternating round by round."""
+    keys = ("temporal_ms", "snapshot_ms")
+    rows = {c: {k: [] for k in keys + ("wall_ms",)} for c in ("on", "off")}
+    counts = {}
+    model = np.eye(4, dtype=np.float32)
+    for k in range(reps + 1):
+        for case in ("on", "off"):
+            opt = 1 if case == "on" else 0
+            r.temporal_reset()
+            for _ in range(2):
+                r.denoise_temporal("accum", 0.25, download=False, motion_vectors=opt)
+            model[0, 3] = 1e-3 * (1 + k % 2)
+            r.set_mesh_transform(0, model.T.ravel())
+            r.commit_geometry("refit")
+            wall = wall_ms(lambda: (r.denoise_temporal("accum", 0.25, download=False, motion_vectors=opt), r.synchronize()))
+            info = r.temporal_info()
+            assert info["motion_used"] == opt
+            if k:
+                for key in keys:
+                    rows[case][key].append(info[key])
+                rows[case]["wall_ms"].append(wall)
+                counts[case] = {q: info[q] for q in ("moved_pixels", "reprojected_pixels", "reset_pixels", "motion_used")}
+    return {c: {k: spread(v) for k, v in rows[c].items()} | counts[c] for c in rows}
+
+
+AB_KEYS = ("filter_ms", "gbuffer_ms", "temporal_total_ms")
+
+
 def filter_only(w, h, depth, reps):
-    """One process of the A/B: pt_denoise's filter_ms at the defaults on the sphere box."""
-    r = setup_renderer(scenes.sphere_in_box("diffuse"), w, h, depth)
+    """One process of the A/B, on the sphere box at the defaults: pt_denoise's filter_ms, gbuffer_ms of
+    a call after a camera nudge, and the device time of a static pt_denoise_temporal call."""
+    sc = scenes.sphere_in_box("diffuse")
+    r = setup_renderer(sc, w, h, depth)
     r.accum_clear()
     r.render_frames(1, 4)
-    ms = []
-    for _ in range(reps + 1):
+    base = np.asarray(sc.camera_blender_pos, np.float32)
+    ms = {k: [] for k in AB_KEYS}
+    for k in range(reps + 1):
+        r.SetCameraBlender(base + np.float32([1e-3 * (k % 2), 0.0, 0.0]), sc.camera_blender_rot, sc.fov_deg)
         r.denoise("accum", 0.25, download=False)
-        ms.append(r.denoise_info()["filter_ms"])
+        info = r.denoise_info()
+        ms["filter_ms"].append(info["filter_ms"])
+        ms["gbuffer_ms"].append(info["gbuffer_ms"])
+        for _ in range(3):
+            r.denoise_temporal("accum", 0.25, download=False)
+        t = r.temporal_info()
+        ms["temporal_total_ms"].append(t["temporal_ms"] + t["variance_ms"] + t["filter_ms"])
     r.close()
-    print(json.dumps(spread(ms[1:])), flush=True)
+    print(json.dumps({k: spread(v[1:]) for k, v in ms.items()}), flush=True)
 
 
 def ab(other, a):
@@ -129,12 +176,13 @@ def ab(other, a):
                 env["PTAMD_LIB"] = str(other)
             p = subprocess.run(cmd, env=env, capture_output=True, text=True, check=True)
             res[side].append(json.loads(p.stdout.strip().splitlines()[-1]))
-    out = {"ab": "pt_denoise filter_ms, sphere_box_diffuse, defaults", "size": a.size, "reps": a.reps, "rounds": a.ab_rounds,
-           "a": "this build", "b": Path(other).name + " (the other build)"}
+    out = {"ab": "pt_denoise filter_ms, gbuffer_ms and a static pt_denoise_temporal call, sphere_box_diffuse, defaults",
+           "size": a.size, "reps": a.reps, "rounds": a.ab_rounds, "a": "this build", "b": Path(other).name + " (the other build)"}
     for side in ("a", "b"):
         out[f"{side}_rounds"] = res[side]
-        out[f"{side}_median_of_medians"] = statistics.median(x["median"] for x in res[side])
-    out["a_over_b"] = out["a_median_of_medians"] / out["b_median_of_medians"]
+    for key in AB_KEYS:
+        med = {side: statistics.median(x[key]["median"] for x in res[side]) for side in ("a", "b")}
+        out[key] = {"a_median_of_medians": med["a"], "b_median_of_medians": med["b"], "a_over_b": med["a"] / med["b"]}
     line = json.dumps(out)
     print(line, flush=True)
     return line
@@ -190,6 +238,8 @@ def run(name, sc, w, h, depth, reps, iterations):
     out["filter_ms_default"] = r.denoise_info()["filter_ms"]
 
     out["temporal"] = temporal_rows(r, sc, reps)
+    r.SetCameraBlender(sc.camera_blender_pos, sc.camera_blender_rot, sc.fov_deg)
+    out["motion"] = motion_rows(r, reps)
 
     r.set_render_ahead(1)  # every call renders its own frame
     img = np.empty((h, w, 3), np.float32)
