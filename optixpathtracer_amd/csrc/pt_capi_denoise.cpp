@@ -1,5 +1,6 @@
 // pt_capi_denoise.cpp — first-hit feature buffers (pt_aov_*) and the a-trous denoiser (pt_denoise):
-// the G-buffer cache, the filter's launches and the entry points.  The kernels are in pt_aov.hip.
+// the G-buffer cache, the filter's launches and the entry points, and DenoiseCall, the checks and set-up
+// that pt_denoise shares with pt_denoise_temporal.  The kernels are in pt_aov.hip and pt_atrous.h.
 #include "pt_renderer.h"
 
 using namespace pt;
@@ -82,6 +83,68 @@ int gbuffer_prepare(pt_renderer* r) {
     return PT_OK;
 }
 
+int DenoiseCall::err(int code, const char* what) const { return fail(code, std::string(fn) + ": " + what); }
+
+int DenoiseCall::check_source() const {
+    if (!r) return err(PT_ERR_INVALID, "NULL renderer");
+    if (source != PT_DENOISE_SRC_ACCUM && source != PT_DENOISE_SRC_DISPLAY && source != PT_DENOISE_SRC_HOST)
+        return err(PT_ERR_INVALID, "no such source");
+    if (source == PT_DENOISE_SRC_HOST && !host_in) return err(PT_ERR_INVALID, "NULL host_in");
+    return PT_OK;
+}
+
+int DenoiseCall::merge(const pt_denoise_options* opt) {
+    o = kDefaults;
+    if (!versioned_merge(o, opt)) return err(PT_ERR_INVALID, "denoise options struct_size is not set");
+    return PT_OK;
+}
+
+int DenoiseCall::begin(bool reads_sigma_color) {
+    if (o.iterations < 1 || o.iterations > 8) return err(PT_ERR_INVALID, "iterations must be 1..8");
+    if ((reads_sigma_color && !(o.sigma_color > 0.0f)) || !(o.sigma_normal > 0.0f) || !(o.sigma_position > 0.0f))
+        return err(PT_ERR_INVALID, "the sigmas must be > 0");
+    if (!(o.albedo_floor > 0.0f)) return err(PT_ERR_INVALID, "albedo_floor must be > 0");
+    if (r->width == 0) return err(PT_ERR_STATE, "call pt_resize first");
+    if (source == PT_DENOISE_SRC_DISPLAY && !r->display_ready) return err(PT_ERR_STATE, "call pt_display_reset first");
+    PT_HIP(hipSetDevice(r->device), "hipSetDevice");
+    pt_renderer::Aov& A = r->aov;
+    n = (size_t)r->width * (size_t)r->height;
+    const int rc = gbuffer_prepare(r);
+    if (rc) return rc;
+    for (DevBuf<float4>& c : A.d_c)
+        if (c.size() != n) PT_HIP(c.alloc(n), "hipMalloc filter colour");
+    if (A.d_out.size() != 3 * n) PT_HIP(A.d_out.alloc(3 * n), "hipMalloc filter result");
+    src = source == PT_DENOISE_SRC_ACCUM ? r->accum() : r->d_display.get();
+    if (source == PT_DENOISE_SRC_HOST) {
+        if (A.d_in.size() != 3 * n) PT_HIP(A.d_in.alloc(3 * n), "hipMalloc filter source");
+        PT_HIP(hipMemcpyAsync(A.d_in, host_in, sizeof(float) * 3 * n, hipMemcpyHostToDevice, r->stream), "upload source");
+        PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");  // host_in is the caller's again
+        src = A.d_in;
+    }
+    // A/B switch of tools/denoise_bench.py
+    const char* e = std::getenv("PTAMD_DENOISE_LDS");
+    lds = e ? std::atoi(e) : kAtrousLdsDefaultStep;
+    P = AtrousParams{};
+    P.out = A.d_out;
+    P.gn = A.d_gn;
+    P.gp = A.d_gp;
+    P.ga = A.d_ga;
+    P.w = r->width;
+    P.h = r->height;
+    P.inv_n = 1.0f / (o.sigma_normal * o.sigma_normal);
+    P.inv_p = 1.0f / (o.sigma_position * o.sigma_position);
+    P.floor = o.albedo_floor;
+    P.demodulate = o.demodulate != 0;
+    return PT_OK;
+}
+
+int DenoiseCall::finish(float* host_out) const {
+    if (!host_out) return PT_OK;
+    PT_HIP(hipMemcpyAsync(host_out, r->aov.d_out, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, r->stream), "download result");
+    PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
+    return collect_pending(r);
+}
+
 }  // namespace pt
 
 extern "C" {
@@ -110,95 +173,46 @@ const void* pt_aov_device_ptr(pt_renderer* r, int32_t kind) {
 
 int pt_denoise_options_default(pt_denoise_options* o) {
     if (!o) return fail(PT_ERR_INVALID, "pt_denoise_options_default: NULL");
-    const size_t n = versioned_bytes(o);
-    if (n == 0) return fail(PT_ERR_INVALID, "pt_denoise_options_default: struct_size is not set");
-    pt_denoise_options d = kDefaults;
-    d.struct_size = o->struct_size;
-    std::memcpy(o, &d, n);
+    if (!versioned_write(o, kDefaults)) return fail(PT_ERR_INVALID, "pt_denoise_options_default: struct_size is not set");
     return PT_OK;
 }
 
 int pt_denoise(pt_renderer* r, int32_t source, const float* host_in, float scale, const pt_denoise_options* opt,
                float* host_out) {
-    if (!r) return fail(PT_ERR_INVALID, "pt_denoise: NULL renderer");
-    if (source != PT_DENOISE_SRC_ACCUM && source != PT_DENOISE_SRC_DISPLAY && source != PT_DENOISE_SRC_HOST)
-        return fail(PT_ERR_INVALID, "pt_denoise: no such source");
-    if (source == PT_DENOISE_SRC_HOST && !host_in) return fail(PT_ERR_INVALID, "pt_denoise: NULL host_in");
-    pt_denoise_options o = kDefaults;
-    if (opt) {
-        const size_t n = versioned_bytes(opt);
-        if (n == 0) return fail(PT_ERR_INVALID, "pt_denoise: options struct_size is not set");
-        std::memcpy(&o, opt, n);
-    }
-    if (o.iterations < 1 || o.iterations > 8) return fail(PT_ERR_INVALID, "pt_denoise: iterations must be 1..8");
-    if (!(o.sigma_color > 0.0f) || !(o.sigma_normal > 0.0f) || !(o.sigma_position > 0.0f))
-        return fail(PT_ERR_INVALID, "pt_denoise: the sigmas must be > 0");
-    if (!(o.albedo_floor > 0.0f)) return fail(PT_ERR_INVALID, "pt_denoise: albedo_floor must be > 0");
-    if (r->width == 0) return fail(PT_ERR_STATE, "pt_denoise: call pt_resize first");
-    if (source == PT_DENOISE_SRC_DISPLAY && !r->display_ready)
-        return fail(PT_ERR_STATE, "pt_denoise: call pt_display_reset first");
-    PT_HIP(hipSetDevice(r->device), "hipSetDevice");
-    pt_renderer::Aov& A = r->aov;
-    const size_t n = (size_t)r->width * (size_t)r->height;
-    int rc = gbuffer_prepare(r);
+    DenoiseCall c{"pt_denoise", r, source, host_in};
+    int rc = c.check_source();
+    if (!rc) rc = c.merge(opt);
+    if (!rc) rc = c.begin(true);
     if (rc) return rc;
-    for (DevBuf<float4>& c : A.d_c)
-        if (c.size() != n) PT_HIP(c.alloc(n), "hipMalloc filter colour");
-    if (A.d_out.size() != 3 * n) PT_HIP(A.d_out.alloc(3 * n), "hipMalloc filter result");
-    const float* src = source == PT_DENOISE_SRC_ACCUM ? r->accum() : r->d_display.get();
-    if (source == PT_DENOISE_SRC_HOST) {
-        if (A.d_in.size() != 3 * n) PT_HIP(A.d_in.alloc(3 * n), "hipMalloc filter source");
-        PT_HIP(hipMemcpyAsync(A.d_in, host_in, sizeof(float) * 3 * n, hipMemcpyHostToDevice, r->stream), "upload source");
-        PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");  // host_in is the caller's again
-        src = A.d_in;
-    }
-    // A/B switch of tools/denoise_bench.py: the largest step whose iteration stages its tile in LDS
-    const char* e = std::getenv("PTAMD_DENOISE_LDS");
-    const int lds = e ? std::atoi(e) : kAtrousLdsDefaultStep;
-
-    AtrousParams P{};
-    P.out = A.d_out;
-    P.gn = A.d_gn;
-    P.gp = A.d_gp;
-    P.ga = A.d_ga;
-    P.w = r->width;
-    P.h = r->height;
-    P.inv_n = 1.0f / (o.sigma_normal * o.sigma_normal);
-    P.inv_p = 1.0f / (o.sigma_position * o.sigma_position);
-    P.floor = o.albedo_floor;
-    P.demodulate = o.demodulate != 0;
+    pt_renderer::Aov& A = r->aov;
+    AtrousParams& P = c.P;
     PT_HIP(A.ev_f[0].ensure(), "hipEventCreate");
     PT_HIP(A.ev_f[1].ensure(), "hipEventCreate");
     PT_HIP(hipEventRecord(A.ev_f[0], r->stream), "hipEventRecord");
-    PT_HIP(atrous_pack(src, scale, P.demodulate != 0, P.floor, P.gn, P.ga, A.d_c[0], n, r->stream), "filter pack kernel");
-    for (int i = 0; i < o.iterations; ++i) {
-        const float sc = o.sigma_color * std::ldexp(1.0f, -i);  // sc * 2^-i, exact
+    PT_HIP(atrous_pack(c.src, scale, P.demodulate != 0, P.floor, P.gn, P.ga, A.d_c[0], c.n, r->stream), "filter pack kernel");
+    for (int i = 0; i < c.o.iterations; ++i) {
+        const float sc = c.o.sigma_color * std::ldexp(1.0f, -i);  // sc * 2^-i, exact
         P.inv_c = 1.0f / (sc * sc);
         P.step = 1 << i;
         P.cin = A.d_c[i & 1];
         P.cout = A.d_c[(i & 1) ^ 1];
-        PT_HIP(atrous_iteration(P, i == o.iterations - 1, lds, r->stream), "filter kernel");
+        PT_HIP(atrous_iteration(P, i == c.o.iterations - 1, c.lds, r->stream), "filter kernel");
     }
     PT_HIP(hipEventRecord(A.ev_f[1], r->stream), "hipEventRecord");
     A.f_timed = true;
-    A.iterations = o.iterations;
-    if (!host_out) return PT_OK;
-    PT_HIP(hipMemcpyAsync(host_out, A.d_out, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, r->stream), "download result");
-    PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
-    return collect_pending(r);
+    A.iterations = c.o.iterations;
+    return c.finish(host_out);
 }
 
 float* pt_denoised_device_ptr(pt_renderer* r) { return r ? r->aov.d_out.get() : nullptr; }
 
 int pt_get_denoise_info(pt_renderer* r, pt_denoise_info* out) {
     if (!r || !out) return fail(PT_ERR_INVALID, "pt_get_denoise_info: NULL");
-    const size_t nb = versioned_bytes(out);
-    if (nb == 0) return fail(PT_ERR_INVALID, "pt_get_denoise_info: struct_size is not set");
+    if (!versioned_bytes(out)) return fail(PT_ERR_INVALID, "pt_get_denoise_info: struct_size is not set");
     PT_HIP(hipSetDevice(r->device), "hipSetDevice");
     PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
     pt_renderer::Aov& A = r->aov;
     pt_denoise_info d{};
-    d.struct_size = out->struct_size;
     d.iterations = A.iterations;
     d.gbuffer_renders = A.renders;
     float ms = 0.0f;
@@ -215,7 +229,7 @@ int pt_get_denoise_info(pt_renderer* r, pt_denoise_info* out) {
         PT_HIP(hipMemcpy(&hits, A.d_hits, sizeof hits, hipMemcpyDeviceToHost), "download hit count");
         d.hit_pixels = hits;
     }
-    std::memcpy(out, &d, nb);
+    versioned_write(out, d);
     return collect_pending(r);
 }
 

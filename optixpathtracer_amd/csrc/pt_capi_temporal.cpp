@@ -16,9 +16,9 @@ constexpr int kMotionChannels[kMotionKinds] = {2, 3, 3};
 
 const pt_temporal_options kTemporalDefaults = {(uint32_t)sizeof(pt_temporal_options), 0.2f, 0.2f, 32, 0.9f, 0.02f, 4.0f, 4, 0};
 
+// The history buffers; the scratch colour and result buffers are DenoiseCall::begin's.
 int alloc_temporal(pt_renderer* r, size_t n, bool motion) {
     pt_renderer::Temporal& T = r->temporal;
-    pt_renderer::Aov& A = r->aov;
     if (T.d_tc.size() != n) {
         T.valid = false;
         for (DevBuf<float4>* b : {&T.d_pgn, &T.d_pgp, &T.d_hc, &T.d_m[0], &T.d_m[1]}) PT_HIP(b->alloc(n), "hipMalloc history");
@@ -35,9 +35,6 @@ int alloc_temporal(pt_renderer* r, size_t n, bool motion) {
         if (T.d_pp.size() != n) PT_HIP(T.d_pp.alloc(n), "hipMalloc previous positions");
         for (Event& e : T.ev_s) PT_HIP(e.ensure(), "hipEventCreate");
     }
-    for (DevBuf<float4>& c : A.d_c)
-        if (c.size() != n) PT_HIP(c.alloc(n), "hipMalloc filter colour");
-    if (A.d_out.size() != 3 * n) PT_HIP(A.d_out.alloc(3 * n), "hipMalloc filter result");
     for (Event& e : T.ev) PT_HIP(e.ensure(), "hipEventCreate");
     return PT_OK;
 }
@@ -48,34 +45,21 @@ extern "C" {
 
 int pt_temporal_options_default(pt_temporal_options* o) {
     if (!o) return fail(PT_ERR_INVALID, "pt_temporal_options_default: NULL");
-    const size_t n = versioned_bytes(o);
-    if (n == 0) return fail(PT_ERR_INVALID, "pt_temporal_options_default: struct_size is not set");
-    pt_temporal_options d = kTemporalDefaults;
-    d.struct_size = o->struct_size;
-    std::memcpy(o, &d, n);
+    if (!versioned_write(o, kTemporalDefaults))
+        return fail(PT_ERR_INVALID, "pt_temporal_options_default: struct_size is not set");
     return PT_OK;
 }
 
 int pt_denoise_temporal(pt_renderer* r, int32_t source, const float* host_in, float scale, const pt_temporal_options* topt,
                         const pt_denoise_options* dopt, float* host_out) {
-    if (!r) return fail(PT_ERR_INVALID, "pt_denoise_temporal: NULL renderer");
-    if (source != PT_DENOISE_SRC_ACCUM && source != PT_DENOISE_SRC_DISPLAY && source != PT_DENOISE_SRC_HOST)
-        return fail(PT_ERR_INVALID, "pt_denoise_temporal: no such source");
-    if (source == PT_DENOISE_SRC_HOST && !host_in) return fail(PT_ERR_INVALID, "pt_denoise_temporal: NULL host_in");
+    DenoiseCall c{"pt_denoise_temporal", r, source, host_in};
+    int rc = c.check_source();
+    if (rc) return rc;
     pt_temporal_options t = kTemporalDefaults;
-    if (topt) {
-        const size_t n = versioned_bytes(topt);
-        if (n == 0) return fail(PT_ERR_INVALID, "pt_denoise_temporal: temporal options struct_size is not set");
-        std::memcpy(&t, topt, n);
-    }
-    pt_denoise_options o;
-    o.struct_size = (uint32_t)sizeof o;
-    (void)pt_denoise_options_default(&o);
-    if (dopt) {
-        const size_t n = versioned_bytes(dopt);
-        if (n == 0) return fail(PT_ERR_INVALID, "pt_denoise_temporal: denoise options struct_size is not set");
-        std::memcpy(&o, dopt, n);
-    }
+    if (!versioned_merge(t, topt))
+        return fail(PT_ERR_INVALID, "pt_denoise_temporal: temporal options struct_size is not set");
+    rc = c.merge(dopt);
+    if (rc) return rc;
     if (!(t.alpha > 0.0f && t.alpha <= 1.0f) || !(t.alpha_moments > 0.0f && t.alpha_moments <= 1.0f))
         return fail(PT_ERR_INVALID, "pt_denoise_temporal: alpha and alpha_moments must be in (0, 1]");
     if (t.max_history < 1) return fail(PT_ERR_INVALID, "pt_denoise_temporal: max_history must be >= 1");
@@ -84,36 +68,20 @@ int pt_denoise_temporal(pt_renderer* r, int32_t source, const float* host_in, fl
     if (!(t.plane_distance > 0.0f)) return fail(PT_ERR_INVALID, "pt_denoise_temporal: plane_distance must be > 0");
     if (!(t.sigma_luminance > 0.0f)) return fail(PT_ERR_INVALID, "pt_denoise_temporal: sigma_luminance must be > 0");
     if (t.variance_history < 0) return fail(PT_ERR_INVALID, "pt_denoise_temporal: variance_history must be >= 0");
-    if (o.iterations < 1 || o.iterations > 8) return fail(PT_ERR_INVALID, "pt_denoise_temporal: iterations must be 1..8");
-    if (!(o.sigma_normal > 0.0f) || !(o.sigma_position > 0.0f))
-        return fail(PT_ERR_INVALID, "pt_denoise_temporal: the sigmas must be > 0");
-    if (!(o.albedo_floor > 0.0f)) return fail(PT_ERR_INVALID, "pt_denoise_temporal: albedo_floor must be > 0");
-    if (r->width == 0) return fail(PT_ERR_STATE, "pt_denoise_temporal: call pt_resize first");
-    if (source == PT_DENOISE_SRC_DISPLAY && !r->display_ready)
-        return fail(PT_ERR_STATE, "pt_denoise_temporal: call pt_display_reset first");
-    PT_HIP(hipSetDevice(r->device), "hipSetDevice");
+    rc = c.begin(false);  // sigma_color is not read
+    if (rc) return rc;
     pt_renderer::Aov& A = r->aov;
     pt_renderer::Temporal& T = r->temporal;
-    const size_t n = (size_t)r->width * (size_t)r->height;
-    int rc = gbuffer_prepare(r);
-    if (rc) return rc;
+    const pt_denoise_options& o = c.o;
+    AtrousParams& P = c.P;
+    const size_t n = c.n;
     const bool motion = t.motion_vectors != 0;
     rc = alloc_temporal(r, n, motion);
     if (rc) {
         T.release();
         return rc;
     }
-    const float* src = source == PT_DENOISE_SRC_ACCUM ? r->accum() : r->d_display.get();
-    if (source == PT_DENOISE_SRC_HOST) {
-        if (A.d_in.size() != 3 * n) PT_HIP(A.d_in.alloc(3 * n), "hipMalloc filter source");
-        PT_HIP(hipMemcpyAsync(A.d_in, host_in, sizeof(float) * 3 * n, hipMemcpyHostToDevice, r->stream), "upload source");
-        PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");  // host_in is the caller's again
-        src = A.d_in;
-    }
-    const char* e = std::getenv("PTAMD_DENOISE_LDS");
-    const int lds = e ? std::atoi(e) : kAtrousLdsDefaultStep;
     const int prev = T.cur, cur = T.cur ^ 1;
-    const bool demodulate = o.demodulate != 0;
 
     TemporalParams K{};
     K.c = A.d_c[0];
@@ -147,23 +115,11 @@ int pt_denoise_temporal(pt_renderer* r, int32_t source, const float* host_in, fl
     K.ntri = r->ntri;
     const bool had_history = T.valid;
 
-    AtrousParams P{};
-    P.out = A.d_out;
-    P.gn = A.d_gn;
-    P.gp = A.d_gp;
-    P.ga = A.d_ga;
-    P.w = r->width;
-    P.h = r->height;
-    P.inv_n = 1.0f / (o.sigma_normal * o.sigma_normal);
-    P.inv_p = 1.0f / (o.sigma_position * o.sigma_position);
-    P.floor = o.albedo_floor;
-    P.demodulate = demodulate;
-
     T.valid = false;  // until every launch below is enqueued
     T.snap_prev = T.mv_last = T.mv_used = T.snap_timed = false;
     PT_HIP(hipMemsetAsync(T.d_count, 0, 3 * sizeof(unsigned long long), r->stream), "hipMemset history counters");
     PT_HIP(hipEventRecord(T.ev[0], r->stream), "hipEventRecord");
-    PT_HIP(atrous_pack(src, scale, demodulate, P.floor, P.gn, P.ga, A.d_c[0], n, r->stream), "filter pack kernel");
+    PT_HIP(atrous_pack(c.src, scale, P.demodulate != 0, P.floor, P.gn, P.ga, A.d_c[0], n, r->stream), "filter pack kernel");
     PT_HIP(temporal_blend(K, use_motion, r->stream), "temporal kernel");
     PT_HIP(hipEventRecord(T.ev[1], r->stream), "hipEventRecord");
     if (t.variance_history > 1)  // a history is at least 1 long: nothing is shorter than 0 or 1
@@ -178,7 +134,7 @@ int pt_denoise_temporal(pt_renderer* r, int32_t source, const float* host_in, fl
         P.cin = i == 0 ? T.d_tc.get() : i == 1 ? T.d_hc.get() : A.d_c[i & 1].get();
         P.cout = i == 0 ? T.d_hc.get() : A.d_c[(i & 1) ^ 1].get();
         PT_HIP(temporal_luminance_scale(P.cin, P.gn, T.d_den, P.w, P.h, t.sigma_luminance, r->stream), "filter divisor kernel");
-        PT_HIP(temporal_atrous_iteration(P, T.d_den, i == 0 && last ? T.d_hc.get() : nullptr, last, lds, r->stream),
+        PT_HIP(temporal_atrous_iteration(P, T.d_den, i == 0 && last ? T.d_hc.get() : nullptr, last, c.lds, r->stream),
                "temporal filter kernel");
     }
     // this view's guides are the next call's previous ones (the cached G-buffer stays as it is)
@@ -206,10 +162,7 @@ int pt_denoise_temporal(pt_renderer* r, int32_t source, const float* host_in, fl
     T.valid = true;
     T.timed = true;
     T.calls++;
-    if (!host_out) return PT_OK;
-    PT_HIP(hipMemcpyAsync(host_out, A.d_out, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, r->stream), "download result");
-    PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
-    return collect_pending(r);
+    return c.finish(host_out);
 }
 
 int pt_temporal_reset(pt_renderer* r) {
@@ -296,13 +249,11 @@ int pt_motion_download(pt_renderer* r, int32_t kind, void* host, int64_t bytes) 
 
 int pt_get_temporal_info(pt_renderer* r, pt_temporal_info* out) {
     if (!r || !out) return fail(PT_ERR_INVALID, "pt_get_temporal_info: NULL");
-    const size_t nb = versioned_bytes(out);
-    if (nb == 0) return fail(PT_ERR_INVALID, "pt_get_temporal_info: struct_size is not set");
+    if (!versioned_bytes(out)) return fail(PT_ERR_INVALID, "pt_get_temporal_info: struct_size is not set");
     PT_HIP(hipSetDevice(r->device), "hipSetDevice");
     PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
     pt_renderer::Temporal& T = r->temporal;
     pt_temporal_info d{};
-    d.struct_size = out->struct_size;
     d.history_valid = T.valid ? 1 : 0;
     d.calls = T.calls;
     if (T.timed) {
@@ -324,7 +275,7 @@ int pt_get_temporal_info(pt_renderer* r, pt_temporal_info* out) {
             d.snapshot_ms = ms;
         }
     }
-    std::memcpy(out, &d, nb);
+    versioned_write(out, d);
     return collect_pending(r);
 }
 

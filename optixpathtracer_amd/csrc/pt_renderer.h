@@ -474,9 +474,44 @@ template <class T>
 size_t versioned_bytes(const T* s) {
     return s->struct_size < sizeof(uint32_t) ? 0 : std::min<size_t>(s->struct_size, sizeof(T));
 }
+// `into` holds the defaults and takes what the caller's struct (or NULL) has of them; the bytes as above.
+template <class T>
+size_t versioned_merge(T& into, const T* user) {
+    const size_t n = user ? versioned_bytes(user) : sizeof(T);
+    if (user && n) std::memcpy(&into, user, n);
+    return n;
+}
+// d, under the caller's struct_size, into as much of the caller's struct as that size covers; the bytes as above.
+template <class T>
+size_t versioned_write(T* user, T d) {
+    const size_t n = versioned_bytes(user);
+    d.struct_size = user->struct_size;
+    std::memcpy(user, &d, n);
+    return n;
+}
 
 // pt_capi_denoise.cpp
 int gbuffer_prepare(pt_renderer* r);
+// What pt_denoise and pt_denoise_temporal do alike, in the order their checks fire: check_source,
+// merge, begin (the caller's own checks in between), finish.  Errors carry the entry point's name, `fn`.
+struct DenoiseCall {
+    const char* fn;
+    pt_renderer* r;
+    int32_t source;
+    const float* host_in;
+    pt_denoise_options o;  // merge: the defaults under the caller's options
+    size_t n;              // begin: pixels
+    const float* src;      // begin: the source on the device; a host source is uploaded
+    int lds;               // begin: the largest step whose iteration stages its tile in LDS
+    AtrousParams P;        // begin: the fields that every iteration shares
+
+    int err(int code, const char* what) const;
+    int check_source() const;
+    int merge(const pt_denoise_options* opt);
+    // checks o (sigma_color only if it is read) and the state; the G-buffer is current and the buffers exist
+    int begin(bool reads_sigma_color);
+    int finish(float* host_out) const;  // the download, unless host_out is NULL
+};
 
 // pt_capi.cpp
 void mat4_inverse(const float* m, float* out);

@@ -15,8 +15,8 @@
 // the moments of a 7x7 window, staged in LDS with its halo of 3 (a workgroup none of whose pixels
 // needs it returns before staging).
 // k_temporal_lscale: per iteration, the 3x3 Gaussian of the variance as the colour term's divisor.
-// k_tatrous / k_tatrous_rows: the iterations of k_atrous / k_atrous_rows over colour | variance
-// records, with the luminance term in place of the colour distance, staged exactly as those are.
+// LuminanceTerm: the iterations are pt_denoise's own kernels, k_filter / k_filter_rows of pt_atrous.h,
+// over colour | variance records with the luminance term in place of the colour distance.
 // Every load is a 16-byte record except the divisor; the arithmetic is the specification of §11,
 // the same in every variant (-ffp-contract=off); tests/temporal_ref.py restates it in numpy.
 #include "pt_atrous.h"
@@ -28,6 +28,21 @@ namespace {
 __device__ __forceinline__ float luminance(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
 __device__ __forceinline__ float dot3(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ bool finite(float v) { return fabsf(v) <= 3.402823466e+38f; }
+
+// §11 step 1: the world point q through the previous camera.  Where it lands in that camera's image
+// of n pixels across (not tested against the image) means something only in front of the camera.
+struct Reprojection {
+    float clip[4];
+    __device__ __forceinline__ Reprojection(const float* prev_view, const float* prev_proj, f3 q) {
+        const float P[4] = {q.x, q.y, q.z, 1.0f};
+        float vw[4];
+        mat4_mul_vec4(prev_view, P, vw);
+        mat4_mul_vec4(prev_proj, vw, clip);
+    }
+    __device__ __forceinline__ bool in_front() const { return clip[3] > 0.0f; }
+    __device__ __forceinline__ float fx(int n) const { return ((clip[0] / clip[3]) * 0.5f + 0.5f) * (float)n - 0.5f; }
+    __device__ __forceinline__ float fy(int n) const { return ((clip[1] / clip[3]) * 0.5f + 0.5f) * (float)n - 0.5f; }
+};
 
 template <bool MOTION>
 __global__ __launch_bounds__(kBlock) void k_temporal(TemporalParams T) {
@@ -60,13 +75,9 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalParams T) {
             f3 hcol = mk(0.0f, 0.0f, 0.0f);
             float h1 = 0.0f, h2 = 0.0f, hlen = 0.0f;
             if (T.history) {
-                const float P[4] = {rp.x, rp.y, rp.z, 1.0f};
-                float vw[4], clip[4];
-                mat4_mul_vec4(T.prev_view, P, vw);
-                mat4_mul_vec4(T.prev_proj, vw, clip);
-                if (clip[3] > 0.0f) {
-                    const float fx = ((clip[0] / clip[3]) * 0.5f + 0.5f) * (float)T.w - 0.5f;
-                    const float fy = ((clip[1] / clip[3]) * 0.5f + 0.5f) * (float)T.h - 0.5f;
+                const Reprojection R(T.prev_view, T.prev_proj, rp);
+                if (R.in_front()) {
+                    const float fx = R.fx(T.w), fy = R.fy(T.h);
                     // outside this range no tap is inside the image (a NaN is outside)
                     if (fx >= -1.0f && fx < (float)T.w && fy >= -1.0f && fy < (float)T.h) {
                         const float ffx = floorf(fx), ffy = floorf(fy);
@@ -172,13 +183,9 @@ __global__ __launch_bounds__(kBlock) void k_motion_screen(const float4* __restri
     f3 o = mk(0.0f, 0.0f, 0.0f);
     if (history && gn[p].w != 0.0f) {
         const float4 q = pp[p];
-        const float P[4] = {q.x, q.y, q.z, 1.0f};
-        float vw[4], clip[4];
-        mat4_mul_vec4(M.prev_view, P, vw);
-        mat4_mul_vec4(M.prev_proj, vw, clip);
-        if (clip[3] > 0.0f) {
-            const float fx = ((clip[0] / clip[3]) * 0.5f + 0.5f) * (float)w - 0.5f;
-            const float fy = ((clip[1] / clip[3]) * 0.5f + 0.5f) * (float)h - 0.5f;
+        const Reprojection R(M.prev_view, M.prev_proj, mk(q.x, q.y, q.z));
+        if (R.in_front()) {
+            const float fx = R.fx(w), fy = R.fy(h);
             o = mk(fx - (float)x, fy - (float)y, 1.0f);
         }
     }
@@ -199,19 +206,8 @@ __global__ __launch_bounds__(kBlock) void k_temporal_variance(const float4* __re
     if (inside) need = gn[p].w != 0.0f && tm[p].z < vh;
     if (!__syncthreads_or(need ? 1 : 0)) return;
     const int ox = blockIdx.x * kTile - 3, oy = blockIdx.y * kTile - 3;
-    for (int i = threadIdx.x; i < side * side; i += kBlock) {
-        const int gx = ox + i % side, gy = oy + i / side;
-        float4 n = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q = n, m = n;  // n.w = 0: no tap outside the image
-        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
-            const size_t g = (size_t)gy * (size_t)w + (size_t)gx;
-            n = gn[g];
-            q = gp[g];
-            m = tm[g];
-        }
-        sn[i] = n;
-        sp[i] = q;
-        sm[i] = m;
-    }
+    for (int i = threadIdx.x; i < side * side; i += kBlock)
+        stage(gn, gp, tm, w, h, ox + i % side, oy + i / side, sn[i], sp[i], sm[i]);
     __syncthreads();
     if (!need) return;
     const int lp = (y - oy) * side + (x - ox);
@@ -266,172 +262,47 @@ __global__ __launch_bounds__(kBlock) void k_temporal_lscale(const float4* __rest
     den[p] = out;
 }
 
-struct TAtrousParams {
-    AtrousParams A;
-    const float* den;
-    float4* hist;
+// The luminance term of DESIGN.md §11 step 3 for k_filter / k_filter_rows (pt_atrous.h), over colour |
+// variance records: den = the centre's divisor, hist = where the result is stored besides (or NULL).
+struct LuminanceTerm {
+    struct Params {
+        AtrousParams A;
+        const float* den;
+        float4* hist;
+    };
+    static __device__ __host__ const AtrousParams& base(const Params& P) { return P.A; }
+
+    f3 out, acc;
+    float v, den, lum, vacc, wsum;
+
+    __device__ __forceinline__ explicit LuminanceTerm(float4 cp) : out(mk(cp.x, cp.y, cp.z)), v(cp.w) {}
+    __device__ __forceinline__ void begin(const Params& P, size_t p, float4 cp) {
+        den = P.den[p];
+        lum = luminance(cp);
+        acc = mk(0.0f, 0.0f, 0.0f);
+        wsum = 0.0f;
+        vacc = 0.0f;
+    }
+    __device__ __forceinline__ void tap(float k, bool centre, float4 cq, float4 nq, float4 pq, float4, float4 np,
+                                        float4 pp, const AtrousParams& A) {
+        float a = (fabsf(luminance(cq) - lum) / den + d2(nq, np) * A.inv_n) + d2(pq, pp) * A.inv_p;
+        if (centre) a = 0.0f;
+        if (a != a) return;
+        const float w = k * pt_expf_neg(-a);
+        acc = mk(acc.x + cq.x * w, acc.y + cq.y * w, acc.z + cq.z * w);
+        vacc += cq.w * (w * w);
+        wsum += w;
+    }
+    __device__ __forceinline__ void finish() {
+        out = mk(acc.x / wsum, acc.y / wsum, acc.z / wsum);
+        v = vacc / (wsum * wsum);
+    }
+    template <bool LAST>
+    __device__ __forceinline__ void store(const Params& P, size_t p, bool valid) {
+        if (P.hist) P.hist[p] = make_float4(out.x, out.y, out.z, v);
+        filter_store<LAST>(P.A, p, valid, out, v);
+    }
 };
-
-// One tap: q's records against the centre's; lp = luminance(cp), den = the centre's divisor.
-__device__ __forceinline__ void ttap(float k, bool centre, float4 cq, float4 nq, float4 pq, float lp, float den, float4 np,
-                                     float4 pp, const AtrousParams& A, f3& acc, float& vacc, float& wsum) {
-    float a = (fabsf(luminance(cq) - lp) / den + d2(nq, np) * A.inv_n) + d2(pq, pp) * A.inv_p;
-    if (centre) a = 0.0f;
-    if (a != a) return;
-    const float w = k * pt_expf_neg(-a);
-    acc = mk(acc.x + cq.x * w, acc.y + cq.y * w, acc.z + cq.z * w);
-    vacc += cq.w * (w * w);
-    wsum += w;
-}
-
-template <bool LAST>
-__device__ __forceinline__ void tatrous_store(const TAtrousParams& T, size_t p, bool valid, f3 out, float v) {
-    const AtrousParams& A = T.A;
-    if (T.hist) T.hist[p] = make_float4(out.x, out.y, out.z, v);
-    if (LAST) {
-        if (valid && A.demodulate) out = out * albedo_floor(A.ga[p], A.floor);
-        store3(A.out, p, out);
-    } else {
-        A.cout[p] = make_float4(out.x, out.y, out.z, v);
-    }
-}
-
-// k_atrous's tiling: LSTEP > 0 stages (16 + 4 LSTEP)^2 records of 48 B; LSTEP = 0 loads every tap.
-template <bool LAST, int LSTEP>
-__global__ __launch_bounds__(kBlock) void k_tatrous(TAtrousParams T) {
-    const AtrousParams& A = T.A;
-    constexpr bool LDS = LSTEP > 0;
-    constexpr int side = kTile + 4 * LSTEP, kRecords = LDS ? side * side : 1;
-    __shared__ float4 sc[kRecords], sn[kRecords], sp[kRecords];
-    int x, y;
-    tile_pixel(x, y);
-    const int s = LDS ? LSTEP : A.step;
-    const int ox = blockIdx.x * kTile - 2 * s, oy = blockIdx.y * kTile - 2 * s;
-    if (LDS) {
-        for (int i = threadIdx.x; i < side * side; i += kBlock) {
-            const int gx = ox + i % side, gy = oy + i / side;
-            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = c, p = c;  // n.w = 0: no tap outside the image
-            if (gx >= 0 && gx < A.w && gy >= 0 && gy < A.h) {
-                const size_t g = (size_t)gy * (size_t)A.w + (size_t)gx;
-                c = A.cin[g];
-                n = A.gn[g];
-                p = A.gp[g];
-            }
-            sc[i] = c;
-            sn[i] = n;
-            sp[i] = p;
-        }
-        __syncthreads();
-    }
-    if (x >= A.w || y >= A.h) return;
-    const size_t p = (size_t)y * (size_t)A.w + (size_t)x;
-    const int lp = LDS ? (y - oy) * side + (x - ox) : 0;
-    const float4 cp = LDS ? sc[lp] : A.cin[p], np = LDS ? sn[lp] : A.gn[p], pp = LDS ? sp[lp] : A.gp[p];
-    const bool valid = np.w != 0.0f;
-    f3 out = mk(cp.x, cp.y, cp.z);
-    float v = cp.w;
-    if (valid) {
-        const float den = T.den[p], lum = luminance(cp);
-        f3 acc = mk(0.0f, 0.0f, 0.0f);
-        float wsum = 0.0f, vacc = 0.0f;
-#pragma unroll
-        for (int dy = -2; dy <= 2; ++dy) {
-#pragma unroll
-            for (int dx = -2; dx <= 2; ++dx) {
-                const int qx = x + dx * s, qy = y + dy * s;
-                const float k = b3(dy + 2) * b3(dx + 2);
-                float4 cq, nq, pq;
-                if (LDS) {
-                    const int lq = (qy - oy) * side + (qx - ox);
-                    nq = sn[lq];
-                    if (nq.w == 0.0f) continue;
-                    cq = sc[lq];
-                    pq = sp[lq];
-                } else {
-                    if (qx < 0 || qx >= A.w || qy < 0 || qy >= A.h) continue;
-                    const size_t q = (size_t)qy * (size_t)A.w + (size_t)qx;
-                    nq = A.gn[q];
-                    if (nq.w == 0.0f) continue;
-                    cq = A.cin[q];
-                    pq = A.gp[q];
-                }
-                ttap(k, dx == 0 && dy == 0, cq, nq, pq, lum, den, np, pp, A, acc, vacc, wsum);
-            }
-        }
-        out = mk(acc.x / wsum, acc.y / wsum, acc.z / wsum);
-        v = vacc / (wsum * wsum);
-    }
-    tatrous_store<LAST>(T, p, valid, out, v);
-}
-
-// k_atrous_rows's tiling for the steps 8 and 16: 32 columns of 8 rows `STEP` apart, (32 + 4 STEP) x 12 records.
-template <bool LAST, int STEP>
-__global__ __launch_bounds__(kBlock) void k_tatrous_rows(TAtrousParams T) {
-    const AtrousParams& A = T.A;
-    constexpr int kCols = 32, kRows = 8, side = kCols + 4 * STEP, kRecords = side * (kRows + 4);
-    __shared__ float4 sc[kRecords], sn[kRecords], sp[kRecords];
-    const int ox = blockIdx.x * kCols - 2 * STEP;
-    const int y0 = ((int)blockIdx.y / STEP) * (kRows * STEP) + (int)blockIdx.y % STEP;  // tile row 0
-    for (int i = threadIdx.x; i < kRecords; i += kBlock) {
-        const int gx = ox + i % side, gy = y0 + (i / side - 2) * STEP;
-        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = c, p = c;  // n.w = 0: no tap outside the image
-        if (gx >= 0 && gx < A.w && gy >= 0 && gy < A.h) {
-            const size_t g = (size_t)gy * (size_t)A.w + (size_t)gx;
-            c = A.cin[g];
-            n = A.gn[g];
-            p = A.gp[g];
-        }
-        sc[i] = c;
-        sn[i] = n;
-        sp[i] = p;
-    }
-    __syncthreads();
-    const int col = threadIdx.x % kCols, row = threadIdx.x / kCols;
-    const int x = blockIdx.x * kCols + col, y = y0 + row * STEP;
-    if (x >= A.w || y >= A.h) return;
-    const size_t p = (size_t)y * (size_t)A.w + (size_t)x;
-    const int lp = (row + 2) * side + (x - ox);
-    const float4 cp = sc[lp], np = sn[lp], pp = sp[lp];
-    const bool valid = np.w != 0.0f;
-    f3 out = mk(cp.x, cp.y, cp.z);
-    float v = cp.w;
-    if (valid) {
-        const float den = T.den[p], lum = luminance(cp);
-        f3 acc = mk(0.0f, 0.0f, 0.0f);
-        float wsum = 0.0f, vacc = 0.0f;
-#pragma unroll
-        for (int dy = -2; dy <= 2; ++dy) {
-#pragma unroll
-            for (int dx = -2; dx <= 2; ++dx) {
-                const int lq = lp + dy * side + dx * STEP;
-                const float4 nq = sn[lq];
-                if (nq.w == 0.0f) continue;
-                ttap(b3(dy + 2) * b3(dx + 2), dx == 0 && dy == 0, sc[lq], nq, sp[lq], lum, den, np, pp, A, acc, vacc, wsum);
-            }
-        }
-        out = mk(acc.x / wsum, acc.y / wsum, acc.z / wsum);
-        v = vacc / (wsum * wsum);
-    }
-    tatrous_store<LAST>(T, p, valid, out, v);
-}
-
-template <bool LAST>
-hipError_t tatrous_launch(const TAtrousParams& T, int lds_max_step, hipStream_t stream) {
-    const AtrousParams& A = T.A;
-    const dim3 grid = tile_grid(A.w, A.h);
-    const int lstep = A.step <= std::min(lds_max_step, kAtrousLdsMaxStep) ? A.step : 0;
-    // k_tatrous_rows: 32 columns per workgroup; per band of 8 * step rows, one workgroup per row phase
-    const dim3 rows((unsigned)((A.w + 31) / 32), (unsigned)((A.h + 8 * A.step - 1) / (8 * A.step) * A.step));
-    switch (lstep) {
-        case 1: hipLaunchKernelGGL((k_tatrous<LAST, 1>), grid, dim3(kBlock), 0, stream, T); break;
-        case 2: hipLaunchKernelGGL((k_tatrous<LAST, 2>), grid, dim3(kBlock), 0, stream, T); break;
-        case 4: hipLaunchKernelGGL((k_tatrous<LAST, 4>), grid, dim3(kBlock), 0, stream, T); break;
-        case 8: hipLaunchKernelGGL((k_tatrous_rows<LAST, 8>), rows, dim3(kBlock), 0, stream, T); break;
-        case 16: hipLaunchKernelGGL((k_tatrous_rows<LAST, 16>), rows, dim3(kBlock), 0, stream, T); break;
-        default: hipLaunchKernelGGL((k_tatrous<LAST, 0>), grid, dim3(kBlock), 0, stream, T); break;
-    }
-    return hipGetLastError();
-}
 
 }  // namespace
 
@@ -473,8 +344,7 @@ hipError_t temporal_luminance_scale(const float4* cin, const float4* gn, float* 
 
 hipError_t temporal_atrous_iteration(const AtrousParams& A, const float* den, float4* hist, bool last, int lds_max_step,
                                      hipStream_t stream) {
-    const TAtrousParams T = {A, den, hist};
-    return last ? tatrous_launch<true>(T, lds_max_step, stream) : tatrous_launch<false>(T, lds_max_step, stream);
+    return filter_iteration<LuminanceTerm>({A, den, hist}, last, lds_max_step, stream);
 }
 
 }  // namespace pt
