@@ -203,6 +203,12 @@ typedef struct pt_stats {
     uint64_t occluder_table_candidates;
     double occluder_table_build_ms;
     uint64_t occluder_table_answers;
+    /* skip table (pt_set_skip_table): device bytes of the words, device time of the last build (both 0
+       while the table is not in use), and the extension rays that carried a skip link, counted by the
+       traversal-statistics kernels like nodes_visited (0 in a render without them) */
+    uint64_t skip_table_bytes;
+    double skip_table_build_ms;
+    uint64_t skip_table_rays;
     /* geometry updates (pt_commit_geometry): commits that changed something, how many of them ended on
        a refitted and how many on a rebuilt tree, and the device time of the last commit's work (HIP
        events around the re-bake, the level refits and the cost reduction, plus the build's own
@@ -336,6 +342,20 @@ int pt_set_occluder_table(pt_renderer* r, int32_t enable);
  * [-1, triangles) is rejected with PT_ERR_INVALID and nothing is written. */
 int pt_occluder_table_download(pt_renderer* r, int64_t* entries_out, int32_t* entries, int64_t bytes);
 int pt_occluder_table_upload(pt_renderer* r, const int32_t* entries, int64_t bytes);
+/* The skip table: two 32-bit words per leaf-order triangle, one for each side of the stored winding,
+ * computed from the triangle records and the BVH alone.  A word is 0 or names the highest BVH4 child
+ * link on the triangle's root-to-leaf path whose whole subtree lies at or below the triangle's plane
+ * on that side.  The fused shading kernels (Lambert, Conductor, Dielectric) store the word with a
+ * continuation ray that climbs from that side (dot(direction, offset direction) > 2^-6), and the
+ * trace kernel drops the named subtree unvisited: no triangle in it can be hit, so images stay
+ * bit-identical.  < 0: automatic (the default: on in the modes where it measured a gain), 0: off,
+ * > 0: on.  Built with the scene and rebuilt by every geometry commit, on the library stream; not
+ * used with vertex coordinates beyond 128 units, and without the memory for it the renderer runs
+ * without it. */
+int pt_set_skip_table(pt_renderer* r, int32_t enable);
+/* Tests: the words for the tree in force (built now if stale).  *words_out = 2 * triangles, or 0 while
+ * the table is not in use; `words` is filled when not NULL and `bytes` = 4 * *words_out. */
+int pt_skip_table_download(pt_renderer* r, int64_t* words_out, uint32_t* words, int64_t bytes);
 
 /* LaunchParams (Renderer/OptiX/LaunchParams.h:9-28) as a C struct: the state one optixLaunch
  * reads.  Same fields and meaning; device pointers where the reference holds device pointers

@@ -153,6 +153,9 @@ class pt_stats(C.Structure):
         ("occluder_table_candidates", C.c_uint64),
         ("occluder_table_build_ms", C.c_double),
         ("occluder_table_answers", C.c_uint64),
+        ("skip_table_bytes", C.c_uint64),
+        ("skip_table_build_ms", C.c_double),
+        ("skip_table_rays", C.c_uint64),
         ("geometry_commits", C.c_uint64),
         ("geometry_refits", C.c_uint64),
         ("geometry_rebuilds", C.c_uint64),
@@ -281,6 +284,8 @@ SIGNATURES = {
     "pt_set_occluder_table": (C.c_int, [_R, C.c_int32]),
     "pt_occluder_table_download": (C.c_int, [_R, C.POINTER(C.c_int64), C.c_void_p, C.c_int64]),
     "pt_occluder_table_upload": (C.c_int, [_R, C.c_void_p, C.c_int64]),
+    "pt_set_skip_table": (C.c_int, [_R, C.c_int32]),
+    "pt_skip_table_download": (C.c_int, [_R, C.POINTER(C.c_int64), C.c_void_p, C.c_int64]),
     "pt_render_accumulate": (C.c_int, [_R, C.c_uint32, C.c_uint32, _FP]),
     "pt_set_accum_device_buffer": (C.c_int, [_R, C.c_void_p]),
     "pt_accum_device_ptr": (C.c_void_p, [_R]),

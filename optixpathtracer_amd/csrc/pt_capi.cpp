@@ -895,6 +895,22 @@ extern "C" int pt_occluder_table_upload(pt_renderer* r, const int32_t* entries, 
     return PT_OK;
 }
 
+extern "C" int pt_set_skip_table(pt_renderer* r, int32_t enable) {
+    if (!r) return fail(PT_ERR_INVALID, "pt_set_skip_table: NULL");
+    const int mode = enable < 0 ? -1 : (enable > 0 ? 1 : 0);
+    r->skip.mode = mode;  // the images do not depend on it: frames rendered ahead stay valid
+    for (pt_renderer* p : r->multi.peers) p->skip.mode = mode;
+    return PT_OK;
+}
+
+// The words for the renderer's state, built now if they are stale; *words_out = 2 * triangles, 0 while
+// the table is not in use.  PT_ERR_INVALID for a buffer of another size.
+extern "C" int pt_skip_table_download(pt_renderer* r, int64_t* words_out, uint32_t* words, int64_t bytes) {
+    if (!r || !words_out) return fail(PT_ERR_INVALID, "pt_skip_table_download: NULL");
+    PT_HIP(hipSetDevice(r->device), "hipSetDevice");
+    return skip_table_download(r, words_out, words, bytes);
+}
+
 extern "C" int pt_set_band_split(pt_renderer* r, int32_t enable) {
     if (!r) return fail(PT_ERR_INVALID, "pt_set_band_split: NULL");
     int rc = collect_pending(r);

@@ -38,6 +38,7 @@ DevLaunch make_launch(const pt_renderer* r, float* accum, uint32_t frame_base, u
     L.lit_words = r->lit.words;
     L.occ_tab = r->lit.active && r->occ.active ? r->occ.d_tab.get() : nullptr;
     L.lit_cells = r->lit.cells;
+    L.skip_tab = r->skip.active ? r->skip.d_words.get() : nullptr;
     return L;
 }
 
@@ -262,6 +263,7 @@ int enqueue_wavefront(pt_renderer* r, const WFPlan& plan, float* accum, uint32_t
     int dev_cus = 256;
     (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, r->device);
     if ((rc = lit_prepare(r)) != PT_OK) return rc;  // before the fork: every stream sees the new bits
+    if ((rc = skip_prepare(r)) != PT_OK) return rc;  // a table switched on since the scene was built
     hipEvent_t a = nullptr, b = nullptr;  // dual: one event pair around the whole call
     if (dual) {
         rc = next_event_pair(r, &a, &b);
@@ -365,6 +367,7 @@ int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, doub
     r->timing.pending = true;
     r->band0_rows = 0;  // set by enqueue_wavefront when this call renders its frame in row bands
     r->lit.active = false;  // the wavefront branch decides (lit_prepare)
+    r->skip.active = false;  // and skip_prepare
     // AUTO = wavefront: it beats the megakernel in every material mode (1080p
     // depth 8, 16 frames per launch, Msamples/s wavefront / megakernel: Lambert 725 / 414,
     // Dielectric 1239 / 758, Default 255 / 104).

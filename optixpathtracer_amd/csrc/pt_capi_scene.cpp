@@ -233,6 +233,8 @@ int build_scene(pt_renderer* r, bool any_tex) {
         if ((rc = sah_cost_now(r, true)) != PT_OK) return rc;
         // lit table: the cells of every leaf-ordered triangle (the bits follow the lights, lit_prepare)
         if ((rc = lit_resubdivide(r)) != PT_OK) return rc;
+        // skip table: built with the scene where the mode uses it (pt_skip.h)
+        if ((rc = skip_prepare(r)) != PT_OK) return rc;
     }
     PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
     return PT_OK;
@@ -289,6 +291,8 @@ int commit_geometry(pt_renderer* r, int how) {
 
     // the lit table's cells follow the records in force; its bits are rebuilt by the next call
     if ((rc = lit_resubdivide(r)) != PT_OK) return rc;
+    // the skip table names links of the tree now in force: rebuilt here, outside any timed render call
+    if ((rc = skip_prepare(r)) != PT_OK) return rc;
     if (rebuild_rc != PT_OK) return fail(rebuild_rc, rebuild_msg);
     return PT_OK;
 }

@@ -45,7 +45,8 @@ constexpr uint64_t pt_stats::*kSummed[] = {
     &pt_stats::nee_unoccluded,
     // the per-kernel ray and byte counts of every device, like trace_kernel_*
     &pt_stats::pair_kernel_rays, &pt_stats::pair_kernel_bytes, &pt_stats::pair_kernel_shadow_rays,
-    &pt_stats::lit_table_answers, &pt_stats::occluder_table_answers, &pt_stats::queue_bytes};
+    &pt_stats::lit_table_answers, &pt_stats::occluder_table_answers, &pt_stats::skip_table_rays,
+    &pt_stats::queue_bytes};
 
 // The lit and occluder tables' figures; the caller has synchronised, so the last builds' events
 // are done.
@@ -81,6 +82,11 @@ int table_stats(pt_renderer* r, pt_stats* out) {
         out->occluder_table_bytes = sizeof(int) * ne;
         out->occluder_table_candidates = (uint64_t)r->occ.built.count;
         out->occluder_table_build_ms = r->occ.built.build_ms;
+    }
+    r->skip.built.harvest();
+    if (skip_wanted(r) && r->skip.d_words && r->skip.built.current(r->skip.version, nullptr, 0)) {
+        out->skip_table_bytes = sizeof(uint32_t) * 2 * (size_t)r->ntri;
+        out->skip_table_build_ms = r->skip.built.build_ms;
     }
     return PT_OK;
 }
@@ -143,6 +149,7 @@ int pt_get_stats(pt_renderer* r, pt_stats* out) {
     out->look_ahead_held = r->ahead.held;
     out->lit_table_answers = c[kCtrLitAnswers];
     out->occluder_table_answers = c[kCtrOccAnswers];
+    out->skip_table_rays = c[kCtrSkipRays];
     if ((rc = table_stats(r, out)) != PT_OK) return rc;
     out->geometry_commits = r->geom.commits;
     out->geometry_refits = r->geom.refits;

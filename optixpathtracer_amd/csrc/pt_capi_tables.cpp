@@ -1,6 +1,7 @@
-// pt_capi_tables.cpp — the lit table and the occluder candidate table: when they are wanted, built and
-// current, and the bodies of their download and upload calls.
+// pt_capi_tables.cpp — the lit table, the occluder candidate table and the skip table: when they are
+// wanted, built and current, and the bodies of their download and upload calls.
 #include "pt_renderer.h"
+#include "pt_skip.h"
 
 using namespace pt;
 
@@ -109,6 +110,55 @@ int lit_prepare(pt_renderer* r) {
     return occ_prepare(r);
 }
 
+// The skip table (pt_skip.h): extension rays drop one proven-unhittable BVH subtree each.
+#ifndef PT_SKIP_TABLE
+#define PT_SKIP_TABLE 1  // auto (pt_set_skip_table < 0): 1 = on where it pays, 0 = off (A/B builds)
+#endif
+bool skip_wanted(const pt_renderer* r) {
+    // the kernels that carry the lookup and the compare: k_shade_fused / k_shade0_pixel and
+    // k_trace_pair of the three fused modes
+    const bool has_code = r->material_mode == PT_MAT_LAMBERT || r->material_mode == PT_MAT_CONDUCTOR ||
+                          r->material_mode == PT_MAT_DIELECTRIC;
+    // auto: Lambert, where three interleaved runs per side at 1080p cleared three parent spreads (+8 %,
+    // DESIGN.md §5 v62); Conductor and Dielectric are not measured with the table on
+    const bool pays = r->material_mode == PT_MAT_LAMBERT;
+    const bool on = r->skip.mode < 0 ? PT_SKIP_TABLE != 0 && pays : r->skip.mode > 0;
+    return on && has_code && r->skip.in_bounds && !r->skip.alloc_failed && r->ntri > 0 && r->bvh_nodes > 0;
+}
+// Decides whether the next launches use the table (r->skip.active) and rebuilds the words on r->stream
+// when the records or the tree have changed since the last build.  Like the lit bits, the build runs
+// on the stream every earlier batch has joined, so batches in flight keep the words they started with.
+int skip_prepare(pt_renderer* r) {
+    r->skip.active = skip_wanted(r);
+    if (!r->skip.active) return PT_OK;
+    if (r->skip.built.current(r->skip.version, nullptr, 0)) return PT_OK;
+    const size_t ntri = (size_t)r->ntri, nn = (size_t)r->bvh_nodes + 1;  // + the scene's sliver flag
+    // hipFree waits for the batches that still read the old arrays
+    if ((2 * ntri > r->skip.d_words.size() && r->skip.d_words.alloc(2 * ntri) != hipSuccess) ||
+        (nn > r->skip.d_node_parent.size() && r->skip.d_node_parent.alloc(nn) != hipSuccess) ||
+        (ntri > r->skip.d_tri_parent.size() && r->skip.d_tri_parent.alloc(ntri) != hipSuccess)) {
+        (void)hipGetLastError();  // not an error: no table
+        r->skip.alloc_failed = true;
+        r->skip.active = false;
+        return PT_OK;
+    }
+    int rc = r->skip.built.begin(r->stream);
+    if (rc != PT_OK) return rc;
+    PT_HIP(skip_build(r->scene(), r->skip.d_node_parent, r->skip.d_tri_parent, r->skip.d_words, r->stream), "skip_build");
+    return r->skip.built.end(r->stream, r->skip.version, nullptr, 0);
+}
+
+int skip_table_download(pt_renderer* r, int64_t* words_out, uint32_t* words, int64_t bytes) {
+    int rc = skip_prepare(r);
+    if (rc) return rc;
+    *words_out = r->skip.active ? 2 * (int64_t)r->ntri : 0;
+    if (!r->skip.active || !words) return PT_OK;
+    if (bytes != (int64_t)sizeof(uint32_t) * *words_out) return fail(PT_ERR_INVALID, "pt_skip_table_download: size mismatch");
+    PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
+    PT_HIP(hipMemcpy(words, r->skip.d_words, (size_t)bytes, hipMemcpyDeviceToHost), "download skip table");
+    return PT_OK;
+}
+
 // The lit table's cells for the leaf-ordered records in force (pt_create, and every geometry
 // commit): lit_subdivide on a host copy; a scene outside the table's limits runs without it until
 // a later commit brings it back inside.  The bits are stale either way (lit.version).
@@ -121,6 +171,12 @@ int lit_resubdivide(pt_renderer* r) {
     float diag = 0.0f;
     r->lit.version++;
     r->lit.built.invalidate_count();
+    // the skip table follows the same records (and the tree they were built or refitted into)
+    r->skip.version++;
+    r->skip.alloc_failed = false;
+    r->skip.in_bounds = true;
+    for (size_t t = 0; t < ntri && r->skip.in_bounds; ++t)
+        r->skip.in_bounds = skip_tri_in_bounds(reinterpret_cast<const float*>(isect_host.data()), (int)t);
     if (!lit_subdivide(isect_host.data(), (int)ntri, lit_words_host, &cells, &diag)) {
         r->lit.d_tri.reset();  // lit_wanted: no table
         r->lit.cells = r->lit.words = 0;

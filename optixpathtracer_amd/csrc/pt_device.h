@@ -103,6 +103,9 @@ struct DevLaunch {
     // leaf-order triangle the shading kernels test before they emit a shadow ray; NULL = not in use
     const int* occ_tab;
     uint32_t lit_cells;
+    // skip table (pt_skip.h): skip_tab[2 * triangle + side] = 0 or the BVH4 child link a continuation
+    // ray leaving that side drops unvisited (fused wavefront modes); NULL = not in use
+    const uint32_t* skip_tab;
 };
 // Slots of DevLaunch::counters (pt_get_stats and pt_get_trace_coherence read them back).
 enum Counter : int {
@@ -131,9 +134,10 @@ enum Counter : int {
     kCtrCohLanes = kCtrCoh0 + 6,  // then the lanes that loaded a global node
     kCtrLitAnswers,       // NEE tests the lit table answered (pt_stats lit_table_answers)
     kCtrOccAnswers,       // NEE tests the occluder candidate table answered
+    kCtrSkipRays,         // extension rays that carried a skip link (pt_stats skip_table_rays; STATS kernels)
     kCounters
 };
-static_assert(kCtrCoh0 == 20 && kCounters == 29, "the counter slots keep their numbers");
+static_assert(kCtrCoh0 == 20 && kCounters == 30, "the counter slots keep their numbers");
 constexpr int kDebugMaxBounces = 64;
 constexpr int kDebugRecordFloats = 22;  // ptamd.h pt_debug_bounce
 
@@ -178,6 +182,7 @@ struct TravStats {
     uint32_t nodes = 0, tris = 0, rays = 0, overflow = 0, retrace = 0;
     uint32_t lds_nodes = 0;  // node visits served from the staged top levels (stage_top_nodes)
     uint32_t unocc = 0;      // k_trace_pair: shadow rays that found their light unoccluded
+    uint32_t skips = 0;      // k_trace_pair: extension rays that carried a skip link (pt_skip.h)
     // wave schedule (trace_range, lane 0 of each wave): iterations, active lanes summed over
     // them, iterations running the node half / the triangle half, refill blocks
     uint32_t steps = 0, active = 0, node_steps = 0, tri_steps = 0, refills = 0;
@@ -346,12 +351,15 @@ struct TravState {
     bool strict;       // re-trace: only acceptable hits are taken (trav_restart_strict)
     int path;          // closest-hit wavefront rays: the path id for the hit record; any-hit
                        // rays: the bits of the hit's t once they stop (trav_result_ok)
+    int skip;          // kRayMixedSkip traversals: the child link this ray drops unvisited (pt_skip.h),
+                       // kEmptyChild = none
     Hit h;
 };
 
 // Ray kinds of a traversal (the ANY template argument): closest hit, any hit (shadow rays,
-// stop at the first hit), or mixed queues where TravState::any decides per lane.
-enum { kRayClosest = 0, kRayAny = 1, kRayMixed = 2 };
+// stop at the first hit), or mixed queues where TravState::any decides per lane; kRayMixedSkip: a
+// mixed queue whose lanes also honour TravState::skip (k_trace_pair with the skip table in use).
+enum { kRayClosest = 0, kRayAny = 1, kRayMixed = 2, kRayMixedSkip = 3 };
 
 __device__ __forceinline__ void trav_init(TravState& s, f3 o, f3 d, float tmin, float tmax) {
     s.o = o;
@@ -369,13 +377,14 @@ __device__ __forceinline__ void trav_init(TravState& s, f3 o, f3 d, float tmin, 
     s.leaf = kEmptyChild;
     s.any = false;
     s.strict = false;
+    s.skip = kEmptyChild;
     s.h.tri = -1;
     s.h.orig = 0x7fffffff;
 }
 
 template <int ANY>
 __device__ __forceinline__ bool is_any(const TravState& s) {
-    return ANY == kRayAny || (ANY == kRayMixed && s.any);
+    return ANY == kRayAny || ((ANY == kRayMixed || ANY == kRayMixedSkip) && s.any);
 }
 
 // Moller-Trumbore; OptiX barycentric convention (u weights v1, v weights v2); closed
@@ -732,9 +741,14 @@ __device__ __forceinline__ void wave_tri_batch(const DevScene& S, TravState& s, 
 }
 
 // The node half and hand-off of trav_step (the wavefront loop tests triangles in wave batches).
+// kRayMixedSkip: a lane whose node slot holds its skip link (pt_skip.h) drops it here and pops in the
+// same step; the hand-off leaves such a leaf in the node slot for the next step to drop.  One compare
+// per step, at most one lost lane-step per ray.
 template <int ANY, bool STATS, int DEPTH>
 __device__ __forceinline__ bool trav_node_step(const DevScene& S, TravState& s, int* __restrict__ stk, int stride,
                                                int* spill, TravStats& ts) {
+    constexpr bool kSkip = ANY == kRayMixedSkip;
+    if (kSkip && s.cur == s.skip) s.cur = kEmptyChild;
     if (s.cur >= 0) {
         if (STATS) {
             ts.nodes++;
@@ -768,7 +782,7 @@ __device__ __forceinline__ bool trav_node_step(const DevScene& S, TravState& s, 
         s.cur = c0;
     }
     if (s.cur == kEmptyChild) stack_pop<DEPTH>(s, stk, stride, spill);
-    if (s.cur < 0 && s.cur != kEmptyChild && s.leaf == kEmptyChild) {
+    if (s.cur < 0 && s.cur != kEmptyChild && (!kSkip || s.cur != s.skip) && s.leaf == kEmptyChild) {
         s.leaf = s.cur;
         stack_pop<DEPTH>(s, stk, stride, spill);
     }
@@ -853,6 +867,7 @@ __device__ __forceinline__ void camera_ray(const DevLaunch& L, int x, int y, f3&
 // hasMetalRoughTexture = HasAlbedoTex() flag bug, OptixRenderer.cpp:535,540, is not kept).
 struct SurfaceHit {
     f3 pos, ng;
+    bool ng_back;  // ng points against the stored winding's normal e1 x e2 (the skip table's side 1)
     Frame fr;
     f3 wo;        // shading space
     f3 albedo;
@@ -919,7 +934,8 @@ __device__ __forceinline__ void reconstruct(const DevScene& S, const Hit& h, f3 
         }
         Ns = normalize(Ns);
     }
-    if (dot(wo_w, Ng) < 0.0f) Ng = -Ng;
+    const bool ng_flip = dot(wo_w, Ng) < 0.0f;
+    if (ng_flip) Ng = -Ng;
     Ng = normalize(Ng);
     if (dot(Ng, Ns) < 0.0f) Ns = -Ns;
     Ns = normalize(Ns);
@@ -929,6 +945,7 @@ __device__ __forceinline__ void reconstruct(const DevScene& S, const Hit& h, f3 
     }
     s.pos = mk(w * v0.x + u * v1.x + v * v2.x, w * v0.y + u * v1.y + v * v2.y, w * v0.z + u * v1.z + v * v2.z);
     s.ng = Ng;
+    s.ng_back = ng_flip != h.back;  // negation and normalize are exact in the sign
     s.albedo = mk(M0.x, M0.y, M0.z);
     s.metallic = M0.w;
     s.roughness = M1.x;

@@ -141,6 +141,10 @@ hipError_t lit_build(const DevScene& S, const uint32_t* tri_words, uint32_t cell
 // leaf-order triangle that probably occludes the cell's shadow rays; runs after lit_build on `stream`.
 hipError_t occ_build(const DevScene& S, const uint32_t* tri_words, uint32_t cells, uint32_t words,
                      const DevLight* lights, int n_lights, const uint32_t* bits, int* occ, hipStream_t stream);
+// The skip table (pt_skip.h, pt_lit.hip k_skip_build): words[2 t + side] = 0 or the BVH4 child link an
+// extension ray leaving that side of leaf-order triangle t drops unvisited; node_parent (n_nodes + 1
+// ints) and tri_parent (ntri ints) are the build's scratch.  Runs on `stream`.
+hipError_t skip_build(const DevScene& S, int* node_parent, int* tri_parent, uint32_t* words, hipStream_t stream);
 
 // Geometry updates (pt_refit.hip).  RefitMesh: what k_rebake needs of one mesh.
 struct RefitMesh {

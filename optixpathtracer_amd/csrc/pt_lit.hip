@@ -1,8 +1,10 @@
 // pt_lit.hip — builds the lit table (pt_lit.h): the per-triangle subdivision on the host at
 // pt_create, the (light, cell) bits on the GPU whenever the lights change, and after them the
-// occluder candidate of every cell the bits leave to the tracer (k_occ_build).
+// occluder candidate of every cell the bits leave to the tracer (k_occ_build); and the skip table
+// (pt_skip.h) whenever the triangle records or the BVH change.
 #include "pt_internal.h"
 #include "pt_lit.h"
+#include "pt_skip.h"
 
 namespace pt {
 
@@ -192,7 +194,46 @@ __global__ __launch_bounds__(kLitBlock) void k_occ_build(DevScene S, const uint3
     occ[id] = cand;
 }
 
+// The skip table (pt_skip.h): the parent links of the BVH4, then one thread per (side, triangle) --
+// side-major, so that neighbouring lanes climb neighbouring paths -- with the walk stack in LDS as in
+// k_lit_build.
+// node_parent[n_nodes] (zeroed by skip_build) is set when the scene holds a sliver: no box_accept then.
+__global__ __launch_bounds__(kLitBlock) void k_skip_parents(const BNode4* __restrict__ nodes,
+                                                           const float4* __restrict__ isect, int n_nodes,
+                                                           int* __restrict__ node_parent, int* __restrict__ tri_parent) {
+    const int i = (int)(blockIdx.x * kLitBlock + threadIdx.x);
+    if (i < n_nodes && skip_parents_of(nodes, reinterpret_cast<const float*>(isect), i, node_parent, tri_parent))
+        atomicOr(&node_parent[n_nodes], 1);
+}
+
+__global__ __launch_bounds__(kLitBlock) void k_skip_build(DevScene S, const int* __restrict__ node_parent,
+                                                         const int* __restrict__ tri_parent,
+                                                         uint32_t* __restrict__ words) {
+    __shared__ int lds_stack[kLitStack * kLitBlock];
+    const int id = (int)(blockIdx.x * kLitBlock + threadIdx.x);
+    if (id >= 2 * S.ntri) return;
+    const int side = id >= S.ntri ? 1 : 0, t = id - side * S.ntri;
+    words[2 * t + side] = skip_word(S.nodes, reinterpret_cast<const float*>(S.isect), node_parent, tri_parent, t, side,
+                                    lds_stack + threadIdx.x, kLitBlock, kLitStack, node_parent[S.n_nodes] == 0);
+}
+
 }  // namespace
+
+// Rebuilds the skip table of the scene's triangles and nodes on `stream`: words[2 t + side];
+// node_parent (n_nodes + 1 ints, the last one the scene's sliver flag) and tri_parent (ntri ints) are
+// its scratch.
+hipError_t skip_build(const DevScene& S, int* node_parent, int* tri_parent, uint32_t* words, hipStream_t stream) {
+    if (S.ntri <= 0 || S.n_nodes <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(node_parent + S.n_nodes, 0, sizeof(int), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_skip_parents, dim3((unsigned)((S.n_nodes + kLitBlock - 1) / kLitBlock)), dim3(kLitBlock), 0,
+                       stream, S.nodes, S.isect, S.n_nodes, node_parent, tri_parent);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_skip_build, dim3((unsigned)((2 * S.ntri + kLitBlock - 1) / kLitBlock)), dim3(kLitBlock), 0,
+                       stream, S, node_parent, tri_parent, words);
+    return hipGetLastError();
+}
 
 // Rebuilds the occluder candidates of n_lights lights (cells entries each) on `stream`, after the
 // lit bits they skip (lit_build on the same stream).

@@ -344,6 +344,20 @@ struct pt_renderer {
         bool active = false;  // this call's launches read the table (make_launch)
         pt::BuiltTable built;  // count: entries >= 0 of the last build or upload
     } occ;
+    // skip table (pt_skip.h): two words per leaf-ordered triangle, a function of the triangle records
+    // and the BVH numbering alone.  version is bumped wherever either changes (lit_resubdivide: the
+    // scene build and every geometry commit); skip_prepare rebuilds the words on `stream` when they
+    // are stale (a failed allocation means the renderer runs without the table)
+    struct Skip {
+        int mode = -1;  // pt_set_skip_table: < 0 auto, 0 off, > 0 on
+        pt::DevBuf<uint32_t> d_words;              // 2 * ntri
+        pt::DevBuf<int> d_node_parent, d_tri_parent;  // the build's scratch
+        uint32_t version = 1;
+        bool in_bounds = false;  // every vertex within kLitMaxCoord (pt_skip.h)
+        bool alloc_failed = false;
+        bool active = false;  // this call's launches read and write the words (make_launch)
+        pt::BuiltTable built;
+    } skip;
 
     // first-hit feature buffers and the denoiser (pt_capi_denoise.cpp, pt_aov.hip): the G-buffer of
     // the view it was rendered for (gbuffer_prepare renders it again when view_key differs), the
@@ -465,6 +479,9 @@ int lit_table_download(pt_renderer* r, pt_lit_table_info* info, uint32_t* tri_wo
                        int64_t bits_bytes);
 int occ_table_download(pt_renderer* r, int64_t* entries_out, int32_t* entries, int64_t bytes);
 int occ_table_upload(pt_renderer* r, const int32_t* entries, int64_t bytes);
+bool skip_wanted(const pt_renderer* r);
+int skip_prepare(pt_renderer* r);
+int skip_table_download(pt_renderer* r, int64_t* words_out, uint32_t* words, int64_t bytes);
 
 // pt_capi_stats.cpp
 int collect_pending(pt_renderer* r);

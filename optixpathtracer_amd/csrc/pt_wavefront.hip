@@ -34,6 +34,7 @@
 
 #include "pt_internal.h"
 #include "pt_lit.h"
+#include "pt_skip.h"
 
 namespace pt {
 
@@ -164,6 +165,7 @@ __device__ __forceinline__ void flush_trav_stats(unsigned long long* counters, c
     const unsigned long long a = wave_sum_u64(ts.nodes), c = wave_sum_u64(ts.tris), d = wave_sum_u64(ts.rays);
     const unsigned long long e = wave_sum_u64(ts.overflow), r = wave_sum_u64(ts.retrace);
     const unsigned long long l = wave_sum_u64(ts.lds_nodes), u = wave_sum_u64(ts.unocc);
+    const unsigned long long sk = wave_sum_u64(ts.skips);
     if (lane_id() == 0) {  // the wave-schedule counts are kept by every lane alike: lane 0's
         atomicAdd(&counters[kCtrNodes], a);
         atomicAdd(&counters[kCtrTriTests], c);
@@ -177,6 +179,7 @@ __device__ __forceinline__ void flush_trav_stats(unsigned long long* counters, c
         atomicAdd(&counters[kCtrWaveRefills], (unsigned long long)ts.refills);
         atomicAdd(&counters[kCtrLdsNodes], l);
         atomicAdd(&counters[kCtrNeeUnoccluded], u);
+        atomicAdd(&counters[kCtrSkipRays], sk);
         for (int k = 0; k < 6; ++k) atomicAdd(&counters[kCtrCoh0 + k], (unsigned long long)ts.coh[k]);
         atomicAdd(&counters[kCtrCohLanes], (unsigned long long)ts.coh_lanes);
     }
@@ -748,6 +751,33 @@ __device__ __forceinline__ bool occ_answers(const DevScene& S, int t, f3 o, f3 d
     return tri_accept(A, E1, E2, inv, mk(o.x * inv.x, o.y * inv.y, o.z * inv.z), th);
 }
 
+// The skip table (pt_skip.h) in the fused shading kernels.  kSkipCode: the material modes whose kernels
+// carry the lookup (like kOcc, a mode keeps it only where it measured a gain).
+// skip_words: both sides' words of the hit triangle, one 8-byte gather issued beside the surface
+// records.  skip_orient: x = the word of the side sf.ng points to (the stored winding's, or the other
+// where sf.ng_back says so), y = the other side's.  skip_pick: the word of the side continue_path
+// offsets the origin to, +-sf.ng, or 0 ("none") unless the normalised direction d the kernel writes
+// climbs from that side, dot(d, +-sf.ng) > kSkipMinCos in fp32 (a smooth shading normal can send a
+// sampled direction below the geometric plane).  Lambert never samples below the surface
+// (lambert_sample forces z >= 0, as kShareOrigin relies on), so its kernels keep one word.
+template <int MODE>
+constexpr bool kSkipCode = MODE == kModeLambert || MODE == kModeConductor || MODE == kModeDielectric;
+__device__ __forceinline__ uint2 skip_words(const DevLaunch& L, int tri) {
+    return reinterpret_cast<const uint2*>(L.skip_tab)[tri];
+}
+__device__ __forceinline__ uint2 skip_orient(uint2 w, const SurfaceHit& sf) {
+    return sf.ng_back ? make_uint2(w.y, w.x) : w;
+}
+template <int MODE>
+__device__ __forceinline__ bool skip_under(const BSample& bs) {  // continue_path's test
+    return MODE != kModeLambert && dot(bs.dir, mk(0.0f, 0.0f, 1.0f)) < 0.0f;
+}
+__device__ __forceinline__ uint32_t skip_pick(uint2 w, const SurfaceHit& sf, bool under, f3 d) {
+    const float up = dot(d, sf.ng);
+    const bool climbs = (under ? -up : up) > kSkipMinCos;
+    return climbs ? (under ? w.y : w.x) : 0u;
+}
+
 // Bounce-0 shadow dedup (with primary dedup): a pixel's first hit is the same in every frame
 // of the batch, so its shadow ray toward light li is too.  k_shadow0_setup builds one shadow
 // ray per (pixel, light) from the frame-0 hit, k_shadow_vis traces them into W.vis[light *
@@ -810,6 +840,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
     __shared__ int lds_occ[kOcc ? kWaves : 1];
     const bool lit = !vis0 && L.lit_tri;  // the lit table answers this bounce's NEE tests where it can
     const bool occ = kOcc && lit && L.occ_tab;
+    const bool skip = kSkipCode<MODE> && L.skip_tab;  // continuation rays carry a skip word (pt_skip.h)
     if (blockIdx.x == 0 && threadIdx.x == 0 && L.counters) atomicAdd(&L.counters[kCtrShadeItems], (unsigned long long)n);
     if ((int)(blockIdx.x * kBlock) >= n) return;  // block-uniform
     {
@@ -822,6 +853,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
         float stmax = 0.0f;
         int path = 0;
         int occ_t = -1;  // the shadow ray's entry of the occluder table: -1 or a triangle
+        uint32_t skip_w = 0;  // the continuation ray's skip word
         const int P1 = L.width * L.height;
         float4 l0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // shade0: the path's radiance after bounce 0
         if (valid) {
@@ -835,6 +867,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
             const Hit h = decode_hit(hv);
             if (h.tri >= 0) {  // a miss ends the path (__miss__radiance :576-583)
                 const int lit_c = lit ? lit_cell(L, h) : -1;  // fetched beside the surface records
+                const uint2 skip2 = skip ? skip_words(L, h.tri) : make_uint2(0u, 0u);  // and so are both sides' words
                 const float4 c = shade0 ? ldqs(rd + path % P1) : c_q;
                 d = mk(c.x, c.y, c.z);
                 SurfaceHit sf;
@@ -893,6 +926,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
                     bsdf_sample<MODE>(seed, sf.albedo, sf.roughness, conductor, sf.wo, bs)) {
                     emit_next = continue_path(sf, bs, beta, o, d, b + 1, L.max_bounces);
                     if (!kBetaQ) stqs(W.beta + path, make_float4(beta.x, beta.y, beta.z, __uint_as_float(seed)));
+                    if (kSkipCode<MODE> && skip) skip_w = skip_pick(skip_orient(skip2, sf), sf, skip_under<MODE>(bs), d);
                 }
             }
         }
@@ -902,7 +936,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
         if (lit) lit_count_block<kWaves>(L, lds_lit);
         if (emit_next) {
             stqs(no + qi, make_float4(o.x, o.y, o.z, __int_as_float(path)));
-            stqs(nd + qi, make_float4(d.x, d.y, d.z, 0.0f));
+            stqs(nd + qi, make_float4(d.x, d.y, d.z, __uint_as_float(skip_w)));
             if (kBetaQ) stqs(queue_beta(W, b + 1) + qi, make_float4(beta.x, beta.y, beta.z, __uint_as_float(seed)));
         }
         if constexpr (kOcc) {
@@ -953,13 +987,17 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
     const bool valid = p < P1 && !wf_cancelled(W);  // a cancelled wave still joins the appends
     int tri = -1;
     SurfaceHit sf;
+    const bool skip = kSkipCode<MODE> && L.skip_tab;  // as k_shade_fused
+    uint2 skip2 = make_uint2(0u, 0u);
     if (valid) {
         const float4 hv = W.hit[p];
         const Hit h = decode_hit(hv);
         tri = h.tri;
         if (tri >= 0) {
+            if (skip) skip2 = skip_words(L, tri);
             const float4 c = W.ray_d[0][p];
             reconstruct<TEX>(S, h, mk(c.x, c.y, c.z), sf);
+            skip2 = skip_orient(skip2, sf);
         }
     }
     const int dbg = debug_path_id(L);
@@ -971,6 +1009,7 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
         f3 o, d, beta = mk(1.0f, 1.0f, 1.0f);
         uint32_t seed = 0;
         float4 l0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        bool under = false;  // the continuation ray's origin is offset against sf.ng (skip_under)
         if (valid && tri >= 0) {
             seed = tea16((uint32_t)(p + L.width * L.row0), L.frame_base + (uint32_t)f);  // devicePrograms.cu:631
             if (path == dbg) debug_record(L, 1, __float_as_int(S.isect[3 * tri].w), sf, beta, mk(0.0f, 0.0f, 0.0f));
@@ -995,13 +1034,16 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
             if (1 < L.max_bounces && bsdf_sample<MODE>(seed, sf.albedo, sf.roughness, conductor, sf.wo, bs)) {
                 emit_next = continue_path(sf, bs, beta, o, d, 1, L.max_bounces);
                 if (!kBetaQ) stqs(W.beta + path, make_float4(beta.x, beta.y, beta.z, __uint_as_float(seed)));
+                if (kSkipCode<MODE> && skip) under = skip_under<MODE>(bs);
             }
         }
         if (valid) stqs(W.L + path, l0);  // every path of the batch, hit or miss
         const int qi = block_append<kWaves>(cnt(W, 1, kQueue), emit_next, lds_q);
         if (emit_next) {
             stqs(no + qi, make_float4(o.x, o.y, o.z, __int_as_float(path)));
-            stqs(nd + qi, make_float4(d.x, d.y, d.z, 0.0f));
+            // the skip word is picked here, from the pixel's surface: one register less across the appends
+            const uint32_t skip_w = (kSkipCode<MODE> && skip) ? skip_pick(skip2, sf, under, d) : 0u;
+            stqs(nd + qi, make_float4(d.x, d.y, d.z, __uint_as_float(skip_w)));
             if (kBetaQ) stqs(queue_beta(W, 1) + qi, make_float4(beta.x, beta.y, beta.z, __uint_as_float(seed)));
         }
     }
@@ -1011,7 +1053,9 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
 // the same hit points and are independent, so one launch traces both queues (one SIMT tail
 // and one launch instead of two).  Items [0, n_ext) are extension rays (closest hit ->
 // hit records), items [n_ext, n_ext + n_sh) shadow rays (any hit -> deferred NEE add).
-template <bool STATS, bool TEX, int BLK = kBlockTrace>
+// SKIP (the launch's shading kernels store skip words, pt_skip.h): the fourth word of an extension
+// ray's direction record is 0 or the child link the ray drops unvisited; shadow rays carry none.
+template <bool STATS, bool TEX, int BLK = kBlockTrace, bool SKIP = false>
 __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, WFState W, int b,
                                                                       unsigned long long* counters) {
     const int n_ext = *cnt(W, b + 1, kQueue);
@@ -1024,6 +1068,11 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
             const float4 a = ldqs(ro + i), c = ldqs(rd + i);
             trav_init(st, mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), 0.0f, 100.0f);
             st.path = __float_as_int(a.w);
+            if (SKIP) {
+                const int w = __float_as_int(c.w);
+                st.skip = w != 0 ? w : kEmptyChild;
+                if (STATS) ts.skips += w != 0;
+            }
         } else {
             const int j = i - n_ext;
             const float4 c = ldqs(W.sh_d + j), k = ldqs(W.sh_c + j);
@@ -1081,7 +1130,7 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
         pool.begin = pool.end = n_all;
     }
     wave_slice(pool.begin, first, end);
-    trace_queue<kRayMixed, STATS, TEX, BLK>(S, first, end, ts, W, fetch, finish, commit, pool);
+    trace_queue<SKIP ? kRayMixedSkip : kRayMixed, STATS, TEX, BLK>(S, first, end, ts, W, fetch, finish, commit, pool);
     if (blockIdx.x == 0 && threadIdx.x == 0 && counters) {
         atomicAdd(&counters[kCtrSegments], (unsigned long long)n_ext);
         atomicAdd(&counters[kCtrShadowRays], (unsigned long long)n_sh);
@@ -1650,7 +1699,9 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
     auto pair = [&](int b) -> hipError_t {
         return trace_timed([&] {
             return trace_variant(tex, wide_trace, stats, [&](auto tx, auto st, auto blk) {
-                return trace_launch(k_trace_pair<st(), tx(), blk()>, blk(), S, W, b, L.counters);
+                return with_flag(L.skip_tab != nullptr, [&](auto sk) {
+                    return trace_launch(k_trace_pair<st(), tx(), blk(), sk()>, blk(), S, W, b, L.counters);
+                });
             });
         });
     };

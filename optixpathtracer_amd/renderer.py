@@ -452,6 +452,22 @@ class OptixRenderer:
         check(self.lib.pt_occluder_table_download(self.h, C.byref(n), e.ctypes.data, e.nbytes), "pt_occluder_table_download")
         return e
 
+    def set_skip_table(self, enable: bool | None) -> None:
+        """pt_set_skip_table: extension rays drop the BVH subtree that lies behind the surface they
+        leave (bit-identical images).  None = automatic (the default), False / True force it."""
+        check(self.lib.pt_set_skip_table(self.h, -1 if enable is None else (1 if enable else 0)), "pt_set_skip_table")
+
+    def skip_table(self):
+        """Tests: the skip words, shape (triangles, 2): 0 or a BVH4 child link per side of the stored
+        winding (pt_skip_table_download); None while the table is not in use."""
+        n = C.c_int64(0)
+        check(self.lib.pt_skip_table_download(self.h, C.byref(n), None, 0), "pt_skip_table_download")
+        if n.value == 0:
+            return None
+        w = np.empty(n.value, np.uint32)
+        check(self.lib.pt_skip_table_download(self.h, C.byref(n), w.ctypes.data, w.nbytes), "pt_skip_table_download")
+        return w.reshape(-1, 2)
+
     def upload_occluder_table(self, entries) -> None:
         """pt_occluder_table_upload: replace the candidates until the next rebuild; every entry must be
         -1 or a triangle index of the scene."""
