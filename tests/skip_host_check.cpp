@@ -12,6 +12,10 @@
 //   (d) "none" only where T has no origin record or a triangle of T's own leaf does not pass.
 // On the closed convex scenes (tetrahedron, cube, sphere) no outward side may be "none", so the
 // sphere's outward words cover at least their own leaf.
+// Four floor scenes (check_floor: a planar floor of 4608 or 18432 triangles under one sphere, with and
+// without a sliver) take the walk to kSkipMaxTris: every word is safe against brute force and no lower
+// than the budget allows, and without a sliver box_accept takes the floor's downward sides to a child of
+// the root.
 // Prints one JSON line: pairs checked, violations, and per scene the words that are "none".
 #include <cmath>
 #include <cstdio>
@@ -318,6 +322,152 @@ Result check(const char* name, const std::vector<Tri>& tris, bool convex) {
     return R;
 }
 
+// A planar floor of quads x quads squares over [-2.4, 2.4]^2 at z = 0 (stored normals +z), one 8x4 sphere
+// above its middle and, with `sliver`, one triangle of aspect 2^-8 away from both.
+std::vector<Tri> floor_scene(int quads, bool sliver) {
+    std::vector<Tri> t;
+    const double s = 4.8 / quads;
+    for (int i = 0; i < quads; ++i)
+        for (int j = 0; j < quads; ++j) {
+            const double x = -2.4 + s * i, y = -2.4 + s * j;
+            push_outward(t, {x, y, 0}, {x + s, y, 0}, {x + s, y + s, 0}, {x, y, -1});
+            push_outward(t, {x, y, 0}, {x + s, y + s, 0}, {x, y + s, 0}, {x, y, -1});
+        }
+    const std::vector<Tri> ball = uv_sphere({0, 0, 0.5}, 0.2, 8, 4);
+    t.insert(t.end(), ball.begin(), ball.end());
+    if (sliver) t.push_back({{3.5, 0, 1}, {4.5, 0, 1}, {4.0, 0.00390625, 1}});
+    return t;
+}
+
+// The floor scenes: large flat regions, where one walk can meet more than kSkipMaxTris triangles.  For
+// every `stride`-th triangle and both sides, the predicate is restated here for all triangles under the
+// path's highest link (heights in long double from the vertices, aspect as smallest height over longest
+// edge) and counted in prefix sums, so that every link of the path is decided by brute force:
+//   (a) the word is on the triangle's path; (b) it is not above the highest link that passes, and the
+//   header's own predicate passes for every triangle under it; (e) it is not below the highest passing
+//   link with at most kSkipMaxTris - 1 triangles under it -- one walk looks at a triangle once, so the
+//   budget cannot run out at or below that link.
+// Counted for the caller: the floor's downward sides and how many of them name a child of the root
+// (all of them without a sliver: box_accept spends no budget), and the words the budget kept lower than
+// the link brute force allows.
+struct FloorResult {
+    Result r;
+    long down = 0, down_root_child = 0, kept_low = 0;
+};
+
+FloorResult check_floor(const char* name, const std::vector<Tri>& tris, bool with_sliver, int stride) {
+    FloorResult F;
+    Result& R = F.r;
+    const Bvh4 B = build(tris);
+    const int n = B.ntri, nn = (int)B.nodes.size();
+    auto fail = [&](const char* what, int t, int side) {
+        if (R.bad++ < 8) std::fprintf(stderr, "%s: %s at triangle %d side %d\n", name, what, t, side);
+    };
+    std::vector<int> node_parent((size_t)nn, -2), tri_parent((size_t)n, -2);
+    bool sliver = false;
+    for (int i = 0; i < nn; ++i)
+        sliver = pt::skip_parents_of(B.nodes.data(), B.isect.data(), i, node_parent.data(), tri_parent.data()) || sliver;
+    if (sliver != with_sliver) fail("the sliver flag", -1, 0);
+    // every triangle once: vertices, whether it counts (aspect >= 2^-6), whether it has words (>= 2^-10)
+    std::vector<double> vtx(9 * (size_t)n);
+    std::vector<char> counts((size_t)n), origin((size_t)n), on_floor((size_t)n);
+    for (int u = 0; u < n; ++u) {
+        double* p = &vtx[9 * (size_t)u];
+        pt::skip_tri_vertices(B.isect.data(), u, p, p + 3, p + 6);
+        long double len[3], area2;
+        {
+            const long double e1[3] = {(long double)p[3] - p[0], (long double)p[4] - p[1], (long double)p[5] - p[2]};
+            const long double e2[3] = {(long double)p[6] - p[0], (long double)p[7] - p[1], (long double)p[8] - p[2]};
+            const long double e3[3] = {e2[0] - e1[0], e2[1] - e1[1], e2[2] - e1[2]};
+            const long double c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+            area2 = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+            len[0] = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+            len[1] = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+            len[2] = std::sqrt(e3[0] * e3[0] + e3[1] * e3[1] + e3[2] * e3[2]);
+        }
+        const long double longest = std::fmax(len[0], std::fmax(len[1], len[2]));
+        const long double aspect = longest > 0 ? (area2 / longest) / longest : 0;  // smallest height / longest edge
+        counts[(size_t)u] = aspect >= 0.015625L;
+        origin[(size_t)u] = aspect >= 0.0009765625L;
+        on_floor[(size_t)u] = p[2] == 0 && p[5] == 0 && p[8] == 0;
+    }
+    auto range_of = [&](int link, int& lo, int& hi) {
+        if (link >= 0) {
+            lo = B.lo[(size_t)link];
+            hi = B.hi[(size_t)link];
+        } else {
+            lo = pt::skip_leaf_first(link);
+            hi = lo + pt::skip_leaf_count(link) - 1;
+        }
+    };
+    std::vector<int> stack(72), pre((size_t)n + 1), path;
+    for (int t = 0; t < n; t += stride)
+        for (int side = 0; side < 2; ++side) {
+            ++R.checked;
+            const uint32_t w = pt::skip_word(B.nodes.data(), B.isect.data(), node_parent.data(), tri_parent.data(), t,
+                                             side, stack.data(), 1, (int)stack.size(), !sliver);
+            path.clear();  // the links from the leaf up to the root's child
+            for (int at = tri_parent[(size_t)t];; at = node_parent[(size_t)(at >> 2)]) {
+                path.push_back(B.nodes[(size_t)(at >> 2)].child[at & 3]);
+                if ((at >> 2) == 0) break;
+            }
+            const double* a = &vtx[9 * (size_t)t];
+            const long double e1[3] = {(long double)a[3] - a[0], (long double)a[4] - a[1], (long double)a[5] - a[2]};
+            const long double e2[3] = {(long double)a[6] - a[0], (long double)a[7] - a[1], (long double)a[8] - a[2]};
+            long double nr[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+            const long double len = std::sqrt(nr[0] * nr[0] + nr[1] * nr[1] + nr[2] * nr[2]);
+            const bool has = origin[(size_t)t] && len > 0;
+            for (auto& x : nr) x = (side ? -x : x) / (len > 0 ? len : 1);
+            const long double top = nr[0] * a[0] + nr[1] * a[1] + nr[2] * a[2] + (long double)pt::kLitDelta;
+            int first, last, passed = 0;  // every link of the path lies inside the highest one's range
+            range_of(path.back(), first, last);
+            const double* q = &vtx[9 * (size_t)first];
+            pre[(size_t)first] = 0;
+            for (int u = first; u <= last; ++u, q += 9) {
+                bool ok = has && counts[(size_t)u];
+                for (int k = 0; k < 9 && ok; k += 3) ok = nr[0] * q[k] + nr[1] * q[k + 1] + nr[2] * q[k + 2] <= top;
+                pre[(size_t)u + 1] = passed += ok ? 1 : 0;
+            }
+            int allowed = -1, floor = -1, got = -1;  // heights on the path, -1 = none
+            for (int k = 0; k < (int)path.size(); ++k) {
+                int lo, hi;
+                range_of(path[(size_t)k], lo, hi);
+                if (pre[(size_t)hi + 1] - pre[(size_t)lo] != hi - lo + 1) break;
+                allowed = k;
+                if (hi - lo + 1 <= pt::kSkipMaxTris - 1) floor = k;
+            }
+            if (w != pt::kSkipNone) {
+                for (int k = 0; k < (int)path.size(); ++k)
+                    if (path[(size_t)k] == (int)w) got = k;
+                if (got < 0) {
+                    fail("(a) the word is not on the triangle's path", t, side);
+                    continue;
+                }
+                pt::SkipOrigin T;
+                int lo, hi;
+                range_of((int)w, lo, hi);
+                bool pass = pt::skip_origin(B.isect.data(), t, side, T);
+                for (int u = lo; u <= hi && pass; ++u)
+                    pass = pt::skip_tri_below(T, &vtx[9 * (size_t)u], &vtx[9 * (size_t)u + 3], &vtx[9 * (size_t)u + 6]);
+                if (!pass) fail("(b) a triangle under the link does not pass the header's predicate", t, side);
+            } else {
+                ++R.none;
+                if (side == 0) ++R.none_outward;
+            }
+            if (got > allowed) fail("(b) a triangle under the link is not below", t, side);
+            if (got < floor) fail("(e) the word is lower than the budget allows", t, side);
+            if (got < allowed) ++F.kept_low;
+            if (on_floor[(size_t)t] && nr[2] < 0) {  // nr points to `side`
+                ++F.down;
+                if (got == (int)path.size() - 1) ++F.down_root_child;
+            }
+        }
+    std::printf("\"%s\": {\"triangles\": %d, \"nodes\": %d, \"none\": %ld, \"none_outward\": %ld, \"checked\": %ld, "
+                "\"down\": %ld, \"down_root_child\": %ld, \"kept_low\": %ld}, ",
+                name, n, nn, R.none, R.none_outward, R.checked, F.down, F.down_root_child, F.kept_low);
+    return F;
+}
+
 }  // namespace
 
 int main() {
@@ -338,6 +488,12 @@ int main() {
     add(check("l_prism", l_prism(), false));
     add(check("quad", quad(), false));
     add(check("soup", soup(200), false));
+    // 4608 floor triangles: more than kSkipMaxTris in the scene, every triangle and side
+    add(check_floor("floor", floor_scene(48, false), false, 1).r);
+    add(check_floor("floor_sliver", floor_scene(48, true), true, 1).r);
+    // 18432: more than kSkipMaxTris under one child of the root, where the budget does run out; every 31st
+    add(check_floor("wide_floor", floor_scene(96, false), false, 31).r);
+    add(check_floor("wide_floor_sliver", floor_scene(96, true), true, 31).r);
     std::printf("\"checked\": %ld, \"none\": %ld, \"bad\": %ld}\n", tot.checked, tot.none, tot.bad);
     return tot.bad ? 1 : 0;
 }

@@ -5,7 +5,9 @@ triangle's plane, which an extension ray that climbs from that side drops unvisi
     differ from the face normals, so rays that dip below the geometric plane fall back to "none"):
     Lambert (auto) and Conductor and Dielectric forced on give the accumulators of the table off, bit
     for bit; so do the textured scene, a scene of one planar mesh, and a renderer whose sphere was moved
-    (against a fresh renderer of the moved scene);
+    (against a fresh renderer of the moved scene); and the same three modes on two open hemispheres,
+    one wound outward and one inward (skip_ref.open_shells), where the reference alone first shows that
+    the other side's word would drop triangles the rays hit;
   * traversal statistics on the same scene: nodes visited and triangle tests per ray are strictly
     lower with the table, the segments equal, and the rays that carried a skip are more than none and
     fewer than the extension rays;
@@ -73,13 +75,44 @@ def off_images():
     return get
 
 
-@pytest.mark.parametrize("name", list(MODES))
-def test_images_unchanged(off_images, name):
+@pytest.fixture(scope="module")
+def shells_tell_sides_apart():
+    """The reference alone (skip_ref.side_swap_hits on the tree the renderer built, traced by the CPU
+    oracle), once: per (hemisphere, side) the (T, side) pairs whose rays hit a triangle under the link
+    that the other side's word names.  Where that is positive a swap of the sides changes hits."""
+    import skip_ref
+    from optixpathtracer_amd.renderer import setup_renderer
+    from oracle.oracle import OracleScene
+
+    sc = skip_ref.open_shells()
+    r = setup_renderer(sc, W, H, DEPTH, kernel=1)
+    nodes, tris = r.bvh_arrays()
+    r.close()
+    o = OracleScene(sc)
+    pairs = skip_ref.side_swap_hits(sc, nodes, tris, lambda rays: o.trace(rays)[0])
+    o.close()
+    return skip_ref.shell_counts(pairs)
+
+
+@pytest.mark.parametrize("scene,name", [("coarse", m) for m in MODES] + [("open_shells", m) for m in MODES],
+                         ids=list(MODES) + [f"open_shells-{m}" for m in MODES])
+def test_images_unchanged(off_images, shells_tell_sides_apart, scene, name):
     mode, skip = MODES[name]
-    sc = _coarse()
-    off, st_off = off_images("coarse", sc, mode)
+    if scene == "open_shells":
+        # two open hemispheres, one wound outward and one inward: on a closed convex mesh the wrong
+        # side's word names nothing a ray can hit; here it names the bowl the ray is inside of, for a
+        # front-face approach (the inward shell's inside, side 0) and a back-face approach (the outward
+        # shell's inside, side 1) alike
+        import skip_ref
+
+        sc = skip_ref.open_shells()
+        print(f"open shells: (T, side) pairs that a side swap would change: {shells_tell_sides_apart}")
+        assert shells_tell_sides_apart[("bowl_outward", 1)] > 0 and shells_tell_sides_apart[("dome_inward", 0)] > 0
+    else:
+        sc = _coarse()
+    off, st_off = off_images(scene, sc, mode)
     on, st_on = _render(sc, mode, skip)
-    _identical(on, off, name)
+    _identical(on, off, f"{scene}, {name}")
     assert off.any()
     assert st_on["segments"] == st_off["segments"] and st_on["shadow_rays"] == st_off["shadow_rays"]
     assert st_off["skip_table_bytes"] == 0 and st_off["skip_table_build_ms"] == 0
