@@ -341,7 +341,10 @@ __device__ __forceinline__ bool alpha_cut(const DevScene& S, int ti, int mi, flo
 // and NaN behaviour as the oracle's tri_hit, without the early exits).  Closest hit is
 // ordered by (t, original triangle index) over the acceptable hits (tri_accept), so the
 // result is independent of BVH shape and visit order.
-struct TravState {
+// TravRay: the ray, its cull distance and its place in the tree -- all the lane-refilling wavefront
+// loop carries in registers (its running hit lives in LDS, TriBatchLds).  TravState adds the running
+// hit of the per-lane traversals (trav_step: megakernel, k_trace, AOV, pt_lit.hip).
+struct TravRay {
     f3 o, d, inv, io;
     float tmin, best;
     int cur, sp, spc;  // current node/leaf, LDS stack depth, entries spilled
@@ -349,10 +352,13 @@ struct TravState {
     int nx, ny, nz;    // byte offset (0 or 16) of the near slab plane per axis within the node
     bool any;          // any-hit ray (only read by kRayMixed traversals)
     bool strict;       // re-trace: only acceptable hits are taken (trav_restart_strict)
-    int path;          // closest-hit wavefront rays: the path id for the hit record; any-hit
-                       // rays: the bits of the hit's t once they stop (trav_result_ok)
+    int path;          // wavefront rays: the path id (closest hit) or the carried word (any hit) for
+                       // finish; per-lane any-hit rays: the bits of the hit's t once they stop
+                       // (trav_result_ok)
     int skip;          // kRayMixedSkip traversals: the child link this ray drops unvisited (pt_skip.h),
                        // kEmptyChild = none
+};
+struct TravState : TravRay {
     Hit h;
 };
 
@@ -361,7 +367,7 @@ struct TravState {
 // mixed queue whose lanes also honour TravState::skip (k_trace_pair with the skip table in use).
 enum { kRayClosest = 0, kRayAny = 1, kRayMixed = 2, kRayMixedSkip = 3 };
 
-__device__ __forceinline__ void trav_init(TravState& s, f3 o, f3 d, float tmin, float tmax) {
+__device__ __forceinline__ void trav_init(TravRay& s, f3 o, f3 d, float tmin, float tmax) {
     s.o = o;
     s.d = d;
     s.inv = safe_inv(d);
@@ -378,12 +384,15 @@ __device__ __forceinline__ void trav_init(TravState& s, f3 o, f3 d, float tmin, 
     s.any = false;
     s.strict = false;
     s.skip = kEmptyChild;
+}
+__device__ __forceinline__ void trav_init(TravState& s, f3 o, f3 d, float tmin, float tmax) {
+    trav_init(static_cast<TravRay&>(s), o, d, tmin, tmax);
     s.h.tri = -1;
     s.h.orig = 0x7fffffff;
 }
 
 template <int ANY>
-__device__ __forceinline__ bool is_any(const TravState& s) {
+__device__ __forceinline__ bool is_any(const TravRay& s) {
     return ANY == kRayAny || ((ANY == kRayMixed || ANY == kRayMixedSkip) && s.any);
 }
 
@@ -412,7 +421,7 @@ __device__ __forceinline__ bool tri_test(const float4 A, const float4 E1, const 
 // Move the bottom (DEPTH / 2) LDS entries to the spill array (rare).  pt_create bounds the
 // BVH depth so the spill never fills (kMaxBvhDepth); a full spill is still counted.
 template <int DEPTH, bool STATS>
-__device__ __forceinline__ void stack_spill(TravState& s, int* __restrict__ stk, int stride, int* spill,
+__device__ __forceinline__ void stack_spill(TravRay& s, int* __restrict__ stk, int stride, int* spill,
                                          TravStats& ts) {
     if (s.spc + (DEPTH / 2) <= kSpillDepth) {
         for (int k = 0; k < (DEPTH / 2); ++k) spill[s.spc + k] = stk[k * stride];
@@ -426,7 +435,7 @@ __device__ __forceinline__ void stack_spill(TravState& s, int* __restrict__ stk,
 
 // LDS stack empty but entries spilled: bring the newest chunk back (rare).
 template <int DEPTH>
-__device__ __forceinline__ void stack_refill(TravState& s, int* __restrict__ stk, int stride, const int* spill) {
+__device__ __forceinline__ void stack_refill(TravRay& s, int* __restrict__ stk, int stride, const int* spill) {
     s.spc -= (DEPTH / 2);
     for (int k = 0; k < (DEPTH / 2); ++k) stk[k * stride] = spill[s.spc + k];
     s.sp = (DEPTH / 2);
@@ -440,7 +449,7 @@ struct NodeLoad {
     int4 ch;
 };
 
-__device__ __forceinline__ NodeLoad node_load(const DevScene& S, const TravState& s, int ni) {
+__device__ __forceinline__ NodeLoad node_load(const DevScene& S, const TravRay& s, int ni) {
     NodeLoad n;
     if (ni < S.n_lds) {  // a top-level node staged in LDS (north_star: "BVH nodes ... staged through LDS")
         const char* b = reinterpret_cast<const char*>(S.lds_nodes + ni);
@@ -490,7 +499,7 @@ __device__ __forceinline__ void stage_top_nodes(DevScene& S, BNode4* top) {
 // min/max per axis, and the plane distances are two children per packed v_pk_fma.  The planes
 // are the ones min/max would choose (fma is monotone in the plane coordinate), so the slab
 // distances equal tri_accept's and the oracle's box_hit's bit for bit.
-__device__ __forceinline__ void node_eval(const NodeLoad& n, const TravState& s, float& t0, float& t1, float& t2,
+__device__ __forceinline__ void node_eval(const NodeLoad& n, const TravRay& s, float& t0, float& t1, float& t2,
                                           float& t3, int& c0, int& c1, int& c2, int& c3) {
     bool h0, h1, h2, h3;
     const float4 ax = n.ax, bx = n.bx, ay = n.ay, by = n.by, az = n.az, bz = n.bz;
@@ -537,7 +546,7 @@ __device__ __forceinline__ void node_eval(const NodeLoad& n, const TravState& s,
 // Test one triangle of the leaf s.leaf and advance it; true when an any-hit ray is done.
 // Closest-hit lanes take a hit by the (t, original index) order; in strict mode
 // (trav_restart_strict) only acceptable hits count.  Any-hit lanes stop at the first hit and
-// record only h.tri (the shadow queue carries the path and contribution in h's other fields).
+// record only h.tri.
 template <int ANY, bool STATS, bool TEX>
 __device__ __forceinline__ bool leaf_tri_eval(const DevScene& S, TravState& s, TravStats& ts, const float4 A,
                                               const float4 E1, const float4 E2) {
@@ -578,7 +587,7 @@ __device__ __forceinline__ bool leaf_tri_step(const DevScene& S, TravState& s, T
 
 // Next stack entry into s.cur (kEmptyChild when the stack is empty).
 template <int DEPTH>
-__device__ __forceinline__ void stack_pop(TravState& s, int* __restrict__ stk, int stride, const int* spill) {
+__device__ __forceinline__ void stack_pop(TravRay& s, int* __restrict__ stk, int stride, const int* spill) {
     if (s.sp == 0 && s.spc > 0) stack_refill<DEPTH>(s, stk, stride, spill);
     const int sp = s.sp - 1;
     const int e = stk[max(sp, 0) * stride];
@@ -641,15 +650,52 @@ __device__ __forceinline__ bool trav_step(const DevScene& S, TravState& s, int* 
 // owner lane) pairs in LDS and tests them 64 at a time, each lane taking one pair and fetching
 // the owner's ray with cross-lane reads.  A pair's hit competes for its owner by the key
 // (t, original index) -- t >= 0, so its bits order as an unsigned integer -- through an LDS
-// 64-bit atomic min; the owner then takes the winner by the closest-hit rule of leaf_tri_eval.
-// The answer is the same (t, index) minimum over acceptable hits as in trav_step.
+// 64-bit atomic min.  The key is the ray's running hit: it lives in the owner's slot from fetch
+// to finish (hit_slot_*), so the unsigned order of the key IS the closest-hit rule of
+// leaf_tri_eval (t smaller, or t equal and original index smaller) and the atomic does the
+// whole update; the owner only reads its cull distance back.  The answer is the same (t, index)
+// minimum over acceptable hits as in trav_step.
 constexpr int kTriPairsPerWave = 256;  // 64 lanes x <= 4 triangles per leaf
 struct TriBatchLds {                    // one per wave
     uint32_t pair[kTriPairsPerWave];    // (leaf-order triangle << 6) | owner lane
-    unsigned long long key[64];         // per owner: min over this round's hits of (t bits << 32 | orig)
+    unsigned long long key[64];         // per owner: min over the ray's hits so far of (t bits << 32 | orig)
     float2 res_uv[64];                  // per owner: the winning pair's u, v
     int res_code[64];                   //   and tri | back << 31 (2.25 KB per wave in all)
 };
+
+// A lane's slot of its wave's TriBatchLds, written at fetch and read at finish.
+//   closest hit: key = (tmax bits, 0x7fffffff): a hit at t == tmax still wins by its index, as with
+//     leaf_tri_eval's initial h.orig; res_uv = 0 and res_code = kMissTri until a pair wins.
+//   any hit: key = (tmax bits, 0xffffffff), above every candidate's key (t <= tmax, index >= 0,
+//     equality at tmax included), so the ray is occluded iff its key moved.  Until then res_uv /
+//     res_code carry three words for the finish of an unoccluded ray (hit_slot_carry); a winning
+//     pair overwrites them, and an occluded ray needs none.
+constexpr int kMissTri = -1;
+__device__ __forceinline__ void hit_slot_carry(TriBatchLds* L, float x, float y, float z) {
+    const int lane = (int)(threadIdx.x & 63);
+    L->res_uv[lane] = make_float2(x, y);
+    L->res_code[lane] = __float_as_int(z);
+}
+__device__ __forceinline__ void hit_slot_init(TriBatchLds* L, float tmax, bool any) {
+    const int lane = (int)(threadIdx.x & 63);
+    L->key[lane] = ((unsigned long long)__float_as_uint(tmax) << 32) | (any ? 0xffffffffull : 0x7fffffffull);
+}
+__device__ __forceinline__ void hit_slot_init_closest(TriBatchLds* L, float tmax) {
+    hit_slot_init(L, tmax, false);
+    hit_slot_carry(L, 0.0f, 0.0f, __int_as_float(kMissTri));
+}
+__device__ __forceinline__ void hit_slot_init_any(TriBatchLds* L, float tmax) { hit_slot_init(L, tmax, true); }
+__device__ __forceinline__ bool hit_slot_occluded(const TriBatchLds* L) {  // any-hit slots
+    return (uint32_t)L->key[threadIdx.x & 63] != 0xffffffffu;
+}
+// (u, v, tri | back << 31) of a closest-hit slot, or the carried words of an unmoved any-hit slot
+__device__ __forceinline__ void hit_slot_words(const TriBatchLds* L, float& x, float& y, float& z) {
+    const int lane = (int)(threadIdx.x & 63);
+    const float2 uv = L->res_uv[lane];
+    x = uv.x;
+    y = uv.y;
+    z = __int_as_float(L->res_code[lane]);
+}
 
 __device__ __forceinline__ int lane_prefix(unsigned long long m) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -657,9 +703,10 @@ __device__ __forceinline__ int lane_prefix(unsigned long long m) {
 
 // Every lane of the wave calls this (wave-uniform control flow); `has` = the lane holds a
 // pending leaf.  Tests all those leaves' triangles, empties the leaf slots and updates the
-// owners' hits.  The trace loop's rays have tmin = 0.
+// owners' slots and cull distances.  True for an any-hit lane whose ray is occluded.  The trace
+// loop's rays have tmin = 0.
 template <int ANY, bool STATS, bool TEX>
-__device__ __forceinline__ void wave_tri_batch(const DevScene& S, TravState& s, bool has, TriBatchLds* L,
+__device__ __forceinline__ bool wave_tri_batch(const DevScene& S, TravRay& s, bool has, TriBatchLds* L,
                                                TravStats& ts) {
     const int lane = (int)(threadIdx.x & 63);
     const int c1 = has ? leaf_count(s.leaf) - 1 : 0;  // 0..3
@@ -674,9 +721,8 @@ __device__ __forceinline__ void wave_tri_batch(const DevScene& S, TravState& s, 
         if (c1 >= 3) L->pair[pre + 3] = ((uint32_t)(first + 3) << 6) | (uint32_t)lane;
         s.leaf = kEmptyChild;
     }
-    L->key[lane] = ~0ull;
-    const int flags = is_any<ANY>(s) ? 2 : 0;
     __builtin_amdgcn_wave_barrier();
+    unsigned long long w = ~0ull;
     for (int base = 0; base < total; base += 64) {  // total is wave-uniform
         const int k = base + lane;
         const bool valid = k < total;
@@ -715,29 +761,13 @@ __device__ __forceinline__ void wave_tri_batch(const DevScene& S, TravState& s, 
             L->res_code[owner] = ti | (bk ? (int)0x80000000 : 0);
         }
         __builtin_amdgcn_wave_barrier();
-        const unsigned long long w = L->key[lane];
-        if (w != ~0ull) {
-            const float tw = __uint_as_float((uint32_t)(w >> 32));
-            const int ow = (int)(uint32_t)w;
-            const float2 ruv = L->res_uv[lane];
-            const float4 r = make_float4(ruv.x, ruv.y, __int_as_float(L->res_code[lane]), 0.0f);
-            const int code = __float_as_int(r.z);
-            if (flags & 2) {  // (this lane's own kind) any hit: done; only h.tri (the record's other fields carry the path)
-                s.h.tri = code & 0x7fffffff;
-                s.path = __float_as_int(tw);
-            } else if (tw < s.best || (tw == s.best && ow < s.h.orig)) {
-                s.best = tw;
-                s.h.t = tw;
-                s.h.u = r.x;
-                s.h.v = r.y;
-                s.h.tri = code & 0x7fffffff;
-                s.h.back = code < 0;
-                s.h.orig = ow;
-            }
-            L->key[lane] = ~0ull;
-        }
+        // the owner's cull distance for the next round and the node steps: the key's t (an any-hit
+        // lane stops after the batch, so its shrunken distance decides nothing)
+        w = L->key[lane];
+        s.best = __uint_as_float((uint32_t)(w >> 32));
         __builtin_amdgcn_wave_barrier();
     }
+    return is_any<ANY>(s) && (uint32_t)w != 0xffffffffu;
 }
 
 // The node half and hand-off of trav_step (the wavefront loop tests triangles in wave batches).
@@ -745,7 +775,7 @@ __device__ __forceinline__ void wave_tri_batch(const DevScene& S, TravState& s, 
 // same step; the hand-off leaves such a leaf in the node slot for the next step to drop.  One compare
 // per step, at most one lost lane-step per ray.
 template <int ANY, bool STATS, int DEPTH>
-__device__ __forceinline__ bool trav_node_step(const DevScene& S, TravState& s, int* __restrict__ stk, int stride,
+__device__ __forceinline__ bool trav_node_step(const DevScene& S, TravRay& s, int* __restrict__ stk, int stride,
                                                int* spill, TravStats& ts) {
     constexpr bool kSkip = ANY == kRayMixedSkip;
     if (kSkip && s.cur == s.skip) s.cur = kEmptyChild;

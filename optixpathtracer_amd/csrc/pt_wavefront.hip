@@ -90,7 +90,6 @@ constexpr int lds_nodes_of() { return BLK == kBlockTrace ? kLdsNodes : PT_LDS_NO
 #define PT_WF_WAVES_TEX 6
 #endif
 constexpr int wf_waves(bool tex) { return tex ? PT_WF_WAVES_TEX : PT_WF_WAVES; }
-constexpr int kMissTri = -1;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
@@ -145,11 +144,12 @@ __global__ void k_hold(WFState W) {
 
 // Hit record of a finished extension ray: (path, u, v, tri | back << 31), or a miss.  The
 // shading kernels reconstruct the surface from (tri, u, v) and never read t, so the first word
-// carries the path id and they skip the ray_o read.
-__device__ __forceinline__ float4 hit_record(const Hit& h, int path) {
-    const float x = __int_as_float(path);
-    return h.tri >= 0 ? make_float4(x, h.u, h.v, __int_as_float(h.tri | (h.back ? (int)0x80000000 : 0)))
-                      : make_float4(x, 0.0f, 0.0f, __int_as_float(kMissTri));
+// carries the path id and they skip the ray_o read.  The last three words are the lane's slot as the
+// triangle batches left it (pt_device.h hit_slot_*).
+__device__ __forceinline__ float4 hit_record(const TriBatchLds* slot, int path) {
+    float u, v, code;
+    hit_slot_words(slot, u, v, code);
+    return make_float4(__int_as_float(path), u, v, code);
 }
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
@@ -436,11 +436,15 @@ __device__ __forceinline__ void stqs(float4* p, float4 v) {
     __builtin_nontemporal_store(pt_v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<pt_v4f*>(p));
 }
 
-// Lane-refilling trace loop over a queue slice: `fetch(ri, state)` initialises lane state
-// for ray ri, `finish(ri, state)` consumes a finished ray.  A finish that returns a token is
-// split in two: its loads are issued before the refill's record loads and `commit(token)` (its
-// stores) runs after them, so the two memory round trips of a batch block overlap
-// (DESIGN.md §5).  A lane whose traversal ends parks
+// Lane-refilling trace loop over a queue slice: `load(ri, state)` loads ray ri's records into the
+// lane's state (origin, direction, tmax in `best`, and whatever else it passes to init in fields
+// that init computes afterwards: the lane's old state is dead, so the records take no registers of
+// their own), `init(ri, state, slot)` completes the state and initialises the lane's hit slot
+// (pt_device.h hit_slot_*); `finish(ri, state, slot)` consumes a finished ray, whose answer is in
+// the slot.  A finish that returns a token is split in two: its loads are issued before the refill's
+// record loads and `commit(token, slot)` (its stores) runs after them, so the two memory round
+// trips of a batch block overlap; commit runs before init, so it still reads the
+// finished ray's slot.  A lane whose traversal ends parks
 // (`done`) until enough lanes are idle; then the wave runs one batch block that finishes the
 // parked rays and refills the idle lanes with the next rays of the slice.  The triangle
 // batches take acceptable hits only (wave_tri_batch), so a finished ray's answer is final.
@@ -472,17 +476,17 @@ struct RayPool {
 
 struct NoCommit {
     template <class T>
-    __device__ void operator()(const T&) const {}
+    __device__ void operator()(const T&, const TriBatchLds*) const {}
 };
-template <int ANY, bool STATS, bool TEX, int BLK, class Fetch, class Finish, class Commit = NoCommit>
+template <int ANY, bool STATS, bool TEX, int BLK, class Load, class Init, class Finish, class Commit = NoCommit>
 __device__ __forceinline__ void trace_range(const DevScene& S, int next, int end, int* stk, TriBatchLds* tri_lds,
-                                            TravStats& ts, const WFState& W, Fetch fetch, Finish finish,
+                                            TravStats& ts, const WFState& W, Load load, Init init, Finish finish,
                                             Commit commit = Commit{}, RayPool pool = RayPool{}) {
-    using Tok = decltype(finish(0, *static_cast<const TravState*>(nullptr)));
+    using Tok = decltype(finish(0, *static_cast<const TravRay*>(nullptr), tri_lds));
     constexpr bool kSplit = !std::is_void_v<Tok>;
     using TokS = std::conditional_t<kSplit, Tok, int>;
     int spill[kSpillDepth];
-    TravState st;
+    TravRay st;
     int ri = -1;
     bool done = false;
     // the slice bounds are wave-uniform: keeping them (and the refill bookkeeping) in SGPRs
@@ -525,23 +529,27 @@ __device__ __forceinline__ void trace_range(const DevScene& S, int next, int end
             const bool fin = done;
             if (done) {  // the triangle batches took acceptable hits only: the answer stands
                 if constexpr (kSplit)
-                    tok = finish(ri, st);
+                    tok = finish(ri, st, tri_lds);
                 else
-                    finish(ri, st);
+                    finish(ri, st, tri_lds);
                 ri = -1;
                 done = false;
             }
             const unsigned long long m = __ballot(ri < 0);
             const int pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            if (ri < 0 && next + pre < end) {
+            const bool take = ri < 0 && next + pre < end;
+            if (take) {
                 ri = next + pre;
-                fetch(ri, st);
-                if (STATS) ts.rays++;
-                done = S.ntri <= 0;  // empty scene: no BVH root, every ray misses
+                load(ri, st);
             }
             next = min(next + (int)__popcll(m), end);
             if constexpr (kSplit) {
-                if (fin) commit(tok);
+                if (fin) commit(tok, tri_lds);
+            }
+            if (take) {
+                init(ri, st, tri_lds);
+                if (STATS) ts.rays++;
+                done = S.ntri <= 0;  // empty scene: no BVH root, every ray misses
             }
 #if PT_CYCLE_PROBE
             if (STATS) ts.refills += (uint32_t)(probe_clock(st.best) - c0);
@@ -573,8 +581,8 @@ __device__ __forceinline__ void trace_range(const DevScene& S, int next, int end
         // the triangles of every pending leaf in one wave batch (pt_device.h wave_tri_batch),
         // then the node half of the step
         if (tri_ok && n_leaf > 0) {  // wave-uniform
-            wave_tri_batch<ANY, STATS, TEX>(S, st, active && st.leaf != kEmptyChild, tri_lds, ts);
-            if (active && is_any<ANY>(st) && st.h.tri >= 0) done = true;
+            const bool occluded = wave_tri_batch<ANY, STATS, TEX>(S, st, active && st.leaf != kEmptyChild, tri_lds, ts);
+            if (active && occluded) done = true;
         }
 #if PT_CYCLE_PROBE
         const uint64_t c2 = probe_clock(st.best);
@@ -609,21 +617,21 @@ __device__ __forceinline__ void trace_range(const DevScene& S, int next, int end
 
 // A trace kernel's queue range [first, end): the workgroup's LDS (per-lane stacks, the staged top
 // BVH levels, the triangle batches), then the lane-refilling loop.
-template <int ANY, bool STATS, bool TEX, int BLK, class Fetch, class Finish, class Commit = NoCommit>
-__device__ __forceinline__ void trace_queue(DevScene S, int first, int end, TravStats& ts, const WFState& W, Fetch fetch,
-                                            Finish finish, Commit commit = Commit{}, RayPool pool = RayPool{}) {
+template <int ANY, bool STATS, bool TEX, int BLK, class Load, class Init, class Finish, class Commit = NoCommit>
+__device__ __forceinline__ void trace_queue(DevScene S, int first, int end, TravStats& ts, const WFState& W, Load load,
+                                            Init init, Finish finish, Commit commit = Commit{}, RayPool pool = RayPool{}) {
     constexpr int kNodes = lds_nodes_of<BLK>();
     __shared__ int stack[kStack * BLK];
     __shared__ BNode4 top[kNodes > 0 ? kNodes : 1];
     __shared__ TriBatchLds tri_batch[BLK / 64];
     stage_top_nodes<kNodes>(S, top);
-    trace_range<ANY, STATS, TEX, BLK>(S, first, end, stack + threadIdx.x, tri_batch + (threadIdx.x >> 6), ts, W, fetch,
-                                      finish, commit, pool);
+    trace_range<ANY, STATS, TEX, BLK>(S, first, end, stack + threadIdx.x, tri_batch + (threadIdx.x >> 6), ts, W, load,
+                                      init, finish, commit, pool);
 }
 
-template <int ANY, bool STATS, bool TEX, int BLK, class Fetch, class Finish>
-__device__ __forceinline__ void trace_slice(const DevScene& S, int n, TravStats& ts, const WFState& W, Fetch fetch,
-                                            Finish finish, int* pool_ctr) {
+template <int ANY, bool STATS, bool TEX, int BLK, class Load, class Init, class Finish>
+__device__ __forceinline__ void trace_slice(const DevScene& S, int n, TravStats& ts, const WFState& W, Load load,
+                                            Init init, Finish finish, int* pool_ctr) {
     int next, end;
     RayPool pool;
     pool.end = n;
@@ -634,7 +642,16 @@ __device__ __forceinline__ void trace_slice(const DevScene& S, int n, TravStats&
         pool.begin = n;
     }
     wave_slice(pool.begin, next, end);
-    trace_queue<ANY, STATS, TEX, BLK>(S, next, end, ts, W, fetch, finish, NoCommit{}, pool);
+    trace_queue<ANY, STATS, TEX, BLK>(S, next, end, ts, W, load, init, finish, NoCommit{}, pool);
+}
+
+// A ray's queue records into the lane's state (trace_range `load`): origin | path and
+// direction | tmax.
+__device__ __forceinline__ void load_ray(TravRay& st, float4 o, float4 d) {
+    st.o = mk(o.x, o.y, o.z);
+    st.path = __float_as_int(o.w);
+    st.d = mk(d.x, d.y, d.z);
+    st.best = d.w;
 }
 
 // Closest hit of queue b.  `dup` > 1 (bounce 0 only): the queue holds `dup` copies of the same
@@ -652,17 +669,18 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_extend(DevScene S, WFSta
     TravStats ts;
     trace_slice<kRayClosest, STATS, TEX, BLK>(
         S, n_trace, ts, W,
-        [&](int ri, TravState& st) {
-            const float4 a = ro[ri], c = rd[ri];
-            trav_init(st, mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), 0.0f, 100.0f);
-            st.path = __float_as_int(a.w);
+        [&](int ri, TravRay& st) { load_ray(st, ro[ri], rd[ri]); },
+        [&](int ri, TravRay& st, TriBatchLds* slot) {
+            trav_init(st, st.o, st.d, 0.0f, 100.0f);
+            hit_slot_init_closest(slot, 100.0f);
         },
-        [&](int ri, const TravState& st) {
+        [&](int ri, const TravRay& st, const TriBatchLds* slot) {
             // copy k of a bounce-0 ray is path st.path + k * n_trace (queue 0 is in path order);
             // copies = 1: k_shade0_pixel reads the pixel's one record for all its frames
+            float4 h = hit_record(slot, st.path);
             for (int k = 0; k < copies; ++k) {
-                float4* rec = W.hit + ri + (size_t)k * n_trace;
-                *rec = hit_record(st.h, st.path + k * n_trace);
+                h.x = __int_as_float(st.path + k * n_trace);
+                W.hit[ri + (size_t)k * n_trace] = h;
             }
         }, cnt(W, b, kPoolExt));
     if (blockIdx.x == 0 && threadIdx.x == 0 && counters) {
@@ -1063,31 +1081,39 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
     const float4* ro = W.ray_o[(b + 1) & 1];
     const float4* rd = W.ray_d[(b + 1) & 1];
     TravStats ts;
-    auto fetch = [&](int i, TravState& st) {
+    // the records of item i into the lane's state: an extension ray's origin | path and direction |
+    // skip word, or a shadow ray's origin | path, direction | tmax and contribution.  st.inv holds the
+    // three words init writes to the slot (pt_device.h hit_slot_carry) until init computes it: the
+    // contribution, or the miss code of a closest-hit slot.
+    auto load = [&](int i, TravRay& st) {
         if (i < n_ext) {
-            const float4 a = ldqs(ro + i), c = ldqs(rd + i);
-            trav_init(st, mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), 0.0f, 100.0f);
-            st.path = __float_as_int(a.w);
-            if (SKIP) {
-                const int w = __float_as_int(c.w);
-                st.skip = w != 0 ? w : kEmptyChild;
-                if (STATS) ts.skips += w != 0;
-            }
+            load_ray(st, ldqs(ro + i), ldqs(rd + i));
+            if (SKIP) st.skip = __float_as_int(st.best);
+            st.best = 100.0f;
+            st.inv = mk(0.0f, 0.0f, __int_as_float(kMissTri));
         } else {
             const int j = i - n_ext;
             const float4 c = ldqs(W.sh_d + j), k = ldqs(W.sh_c + j);
             // origin | path: the shadow ray's own record, or (Lambert) the continuation ray of the
             // same path, which starts at the same point (k_shade_fused)
             const int q = __float_as_int(k.w);
-            const float4 a = ldqs(q >= 0 ? ro + q : W.sh_o + j);
-            trav_init(st, mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), 0.0f, c.w);
-            st.any = true;
-            // an any-hit traversal only writes h.tri: the record's other fields carry the path
-            // and the contribution to finish()
-            st.h.orig = __float_as_int(a.w);
-            st.h.t = k.x;
-            st.h.u = k.y;
-            st.h.v = k.z;
+            load_ray(st, ldqs(q >= 0 ? ro + q : W.sh_o + j), c);
+            st.inv = mk(k.x, k.y, k.z);
+        }
+    };
+    auto init = [&](int i, TravRay& st, TriBatchLds* slot) {
+        const bool any = i >= n_ext;
+        const int skip_w = SKIP ? st.skip : 0;
+        // a shadow ray's slot carries its contribution to commit(); a hit may overwrite it, and an
+        // occluded ray adds nothing
+        hit_slot_init(slot, st.best, any);
+        hit_slot_carry(slot, st.inv.x, st.inv.y, st.inv.z);
+        trav_init(st, st.o, st.d, 0.0f, st.best);
+        st.any = any;
+        if (SKIP) {
+            const bool skips = !any && skip_w != 0;
+            st.skip = skips ? skip_w : kEmptyChild;
+            if (STATS) ts.skips += skips;
         }
     };
     // the deferred NEE add as load (finish, before the refill's record loads) + store (commit,
@@ -1095,26 +1121,26 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
     struct NeeAdd {
         float4* p;
         float4 v;
-        float x, y, z;
     };
-    auto finish = [&](int i, const TravState& st) -> NeeAdd {
-        NeeAdd a{nullptr, make_float4(0.0f, 0.0f, 0.0f, 0.0f), 0.0f, 0.0f, 0.0f};
-        const Hit& h = st.h;
+    auto finish = [&](int i, const TravRay& st, const TriBatchLds* slot) -> NeeAdd {
+        NeeAdd a{nullptr, make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
         // the hit-record stores first: a store issued after the radiance load would wait for it
-        if (i < n_ext) stqs(W.hit + i, hit_record(h, st.path));
+        if (i < n_ext) stqs(W.hit + i, hit_record(slot, st.path));
         __builtin_amdgcn_sched_barrier(0);
-        if (STATS && i >= n_ext && h.tri < 0) ts.unocc++;
-        if (i >= n_ext && h.tri < 0) {  // unoccluded: add the deferred NEE contribution
-            a.p = W.L + h.orig;
+        const bool unocc = i >= n_ext && !hit_slot_occluded(slot);
+        if (STATS && unocc) ts.unocc++;
+        if (unocc) {  // add the deferred NEE contribution
+            a.p = W.L + st.path;
             a.v = *a.p;
-            a.x = h.t;
-            a.y = h.u;
-            a.z = h.v;
         }
         return a;
     };
-    auto commit = [&](const NeeAdd& a) {
-        if (a.p) *a.p = make_float4(a.v.x + a.x, a.v.y + a.y, a.v.z + a.z, 0.0f);
+    auto commit = [&](const NeeAdd& a, const TriBatchLds* slot) {
+        if (a.p) {
+            float x, y, z;
+            hit_slot_words(slot, x, y, z);
+            *a.p = make_float4(a.v.x + x, a.v.y + y, a.v.z + z, 0.0f);
+        }
     };
     // The queue is [extension rays | shadow rays] in contiguous wave slices, so all but one wave
     // trace a single ray kind; a mixed-kind loop serves both (per-kind loops in one kernel and
@@ -1130,7 +1156,7 @@ __global__ __launch_bounds__(BLK, wf_waves(TEX)) void k_trace_pair(DevScene S, W
         pool.begin = pool.end = n_all;
     }
     wave_slice(pool.begin, first, end);
-    trace_queue<SKIP ? kRayMixedSkip : kRayMixed, STATS, TEX, BLK>(S, first, end, ts, W, fetch, finish, commit, pool);
+    trace_queue<SKIP ? kRayMixedSkip : kRayMixed, STATS, TEX, BLK>(S, first, end, ts, W, load, init, finish, commit, pool);
     if (blockIdx.x == 0 && threadIdx.x == 0 && counters) {
         atomicAdd(&counters[kCtrSegments], (unsigned long long)n_ext);
         atomicAdd(&counters[kCtrShadowRays], (unsigned long long)n_sh);
@@ -1238,13 +1264,13 @@ __global__ __launch_bounds__(BLK, wf_waves(false)) void k_shadow_vis(DevScene S,
     TravStats ts;
     trace_slice<kRayAny, false, TEX, BLK>(
         S, n, ts, W,
-        [&](int j, TravState& st) {
-            const float4 a = W.sh_o[j], c = W.sh_d[j];
-            trav_init(st, mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), 0.0f, c.w);
-            st.path = __float_as_int(a.w);
+        [&](int j, TravRay& st) { load_ray(st, W.sh_o[j], W.sh_d[j]); },
+        [&](int j, TravRay& st, TriBatchLds* slot) {
+            trav_init(st, st.o, st.d, 0.0f, st.best);
+            hit_slot_init_any(slot, st.best);
         },
-        [&](int j, const TravState& st) {
-            const bool occluded = st.h.tri >= 0;
+        [&](int j, const TravRay& st, const TriBatchLds* slot) {
+            const bool occluded = hit_slot_occluded(slot);
             W.vis[j] = table ? (occluded ? 0 : 1) : (occluded ? -1 : st.path);
         }, cnt(W, b, kPoolSh));
 }
