@@ -13,6 +13,7 @@
 // DESIGN.md §10, operation for operation and the same in every variant (the build is
 // -ffp-contract=off); tests/test_gpu_denoise.py restates it in numpy and compares bit for bit.
 #include "pt_atrous.h"
+#include "pt_shade.h"
 
 namespace pt {
 
@@ -118,10 +119,9 @@ struct ColourTerm {
 }  // namespace
 
 hipError_t gbuffer_render(const DevScene& S, const DevLaunch& L, const AovBuffers& B, hipStream_t stream) {
-    if (S.texinfo)
-        hipLaunchKernelGGL(k_gbuffer<true>, tile_grid(L.width, L.height), dim3(kBlock), 0, stream, S, L, B);
-    else
-        hipLaunchKernelGGL(k_gbuffer<false>, tile_grid(L.width, L.height), dim3(kBlock), 0, stream, S, L, B);
+    with_flag(S.texinfo != nullptr, [&](auto tx) {
+        hipLaunchKernelGGL(k_gbuffer<tx()>, tile_grid(L.width, L.height), dim3(kBlock), 0, stream, S, L, B);
+    });
     return hipGetLastError();
 }
 

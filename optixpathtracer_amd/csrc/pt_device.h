@@ -1,9 +1,10 @@
-// pt_device.h — HBM layout of the scene, BVH4 traversal and the path integrator for gfx950.
+// pt_device.h — HBM layout of the scene and BVH4 traversal for gfx950.
 //
 // Replaces, for the render path of Damo12320/OptixPathtracer:
 //   * optixTrace + the closed OptiX 7.3 traversal / triangle test (devicePrograms.cu:216-260)
-//   * __closesthit__radiance (devicePrograms.cu:343-514), __miss__radiance/__miss__shadow
-//     (:576-591), SamplePath (:625-664) and the camera of __raygen__renderFrame (:601-623).
+//   * the camera of __raygen__renderFrame (:601-623).
+// What happens at a hit (__closesthit__radiance, :343-514) is pt_shade.h; SamplePath's loop
+// (:625-664) is the megakernel's, pt_render.hip.
 //
 // HBM layout (triangle arrays in LBVH leaf order, 16-byte aligned records):
 //   nodes4 : BNode4[<N], 128 B — 4 child AABBs as SoA float4s + child links; one cache line
@@ -195,6 +196,40 @@ struct TravStats {
     uint64_t probe_t = 0;  // s_memtime when the node half's loads landed
 #endif
 };
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Traversal statistics of a wave into the renderer's counters (Counter above); every lane calls it.  The
+// fields a kernel never counts (the megakernel: LDS nodes, k_trace_pair's two, the wave schedule) add zero.
+template <bool STATS>
+__device__ __forceinline__ void flush_trav_stats(unsigned long long* counters, const TravStats& ts) {
+    if (!STATS || !counters) return;
+    const unsigned long long a = wave_sum_u64(ts.nodes), c = wave_sum_u64(ts.tris), d = wave_sum_u64(ts.rays);
+    const unsigned long long e = wave_sum_u64(ts.overflow), r = wave_sum_u64(ts.retrace);
+    const unsigned long long l = wave_sum_u64(ts.lds_nodes), u = wave_sum_u64(ts.unocc);
+    const unsigned long long sk = wave_sum_u64(ts.skips);
+    if ((threadIdx.x & 63) == 0) {  // the wave-schedule counts are kept by every lane alike: lane 0's
+        atomicAdd(&counters[kCtrNodes], a);
+        atomicAdd(&counters[kCtrTriTests], c);
+        atomicAdd(&counters[kCtrRays], d);
+        atomicAdd(&counters[kCtrStackOverflows], e);
+        atomicAdd(&counters[kCtrRetraces], r);
+        atomicAdd(&counters[kCtrWaveSteps], (unsigned long long)ts.steps);
+        atomicAdd(&counters[kCtrWaveActive], (unsigned long long)ts.active);
+        atomicAdd(&counters[kCtrWaveNodeSteps], (unsigned long long)ts.node_steps);
+        atomicAdd(&counters[kCtrWaveTriSteps], (unsigned long long)ts.tri_steps);
+        atomicAdd(&counters[kCtrWaveRefills], (unsigned long long)ts.refills);
+        atomicAdd(&counters[kCtrLdsNodes], l);
+        atomicAdd(&counters[kCtrNeeUnoccluded], u);
+        atomicAdd(&counters[kCtrSkipRays], sk);
+        for (int k = 0; k < 6; ++k) atomicAdd(&counters[kCtrCoh0 + k], (unsigned long long)ts.coh[k]);
+        atomicAdd(&counters[kCtrCohLanes], (unsigned long long)ts.coh_lanes);
+    }
+}
 
 // ---- ray / box arithmetic shared bit for bit with the oracle ---------------------------------
 // The slab distance of a plane p on axis a is fma(p, inv_a, -io_a) with inv = 1/d (IEEE
@@ -889,219 +924,6 @@ __device__ __forceinline__ void camera_ray(const DevLaunch& L, int x, int y, f3&
     float inv = 1.0f / sqrtf(d4);
     d = mk(pw[0] * inv, pw[1] * inv, pw[2] * inv);
     o = mk(L.cam_pos[0], L.cam_pos[1], L.cam_pos[2]);
-}
-
-// Surface reconstruction at a hit: GetNormal / GetSurfacePos (devicePrograms.cu:83-129),
-// back-face flip (:379-382), SampleTextures + normal mapping (:392-409), BuildTangentSpace
-// (:168-212).  The texture ids are used as given (the reference's hasNormalTexture /
-// hasMetalRoughTexture = HasAlbedoTex() flag bug, OptixRenderer.cpp:535,540, is not kept).
-struct SurfaceHit {
-    f3 pos, ng;
-    bool ng_back;  // ng points against the stored winding's normal e1 x e2 (the skip table's side 1)
-    Frame fr;
-    f3 wo;        // shading space
-    f3 albedo;
-    float metallic, roughness;
-};
-
-__device__ __forceinline__ void apply_textures(const DevScene& S, int ti, float u, float v, const float4 M1,
-                                               const float4 M2, f3& albedo, float& metallic, float& roughness,
-                                               f3& Ns) {
-    const int at = __float_as_int(M1.z), nt = __float_as_int(M1.w), mt = __float_as_int(M2.x);
-    float x, y;
-    tri_texcoord(S, ti, u, v, x, y);
-    f3 ntex = mk(0.0f, 0.0f, 0.0f);
-    if (at >= 0) {
-        const float4 c = tex_sample(S, at, x, y, true);
-        albedo = albedo * mk(c.x, c.y, c.z);
-    }
-    if (nt >= 0) {
-        const float4 c = tex_sample(S, nt, x, y, false);
-        ntex = mk(c.x, c.y, c.z);
-    }
-    if (mt >= 0) {
-        const float4 c = tex_sample(S, mt, x, y, false);
-        metallic = c.x;
-        roughness = c.y;
-    }
-    if (ntex.x != 0.0f || ntex.y != 0.0f || ntex.z != 0.0f) {  // normal mapping in the a8 frame of Ns
-        f3 d1 = cross(Ns, mk(0.0f, 0.0f, 1.0f));
-        f3 d2 = cross(Ns, mk(0.0f, 1.0f, 0.0f));
-        f3 T0 = (length(d1) > length(d2)) ? d1 : d2;
-        T0 = normalize(T0);
-        const f3 B0 = cross(T0, Ns);
-        const f3 tn = mk(ntex.x * 2.0f - 1.0f, ntex.y * 2.0f - 1.0f, ntex.z * 2.0f - 1.0f);
-        Ns = normalize(mk((T0.x * tn.x + B0.x * tn.y) + Ns.x * tn.z, (T0.y * tn.x + B0.y * tn.y) + Ns.y * tn.z,
-                          (T0.z * tn.x + B0.z * tn.y) + Ns.z * tn.z));
-    }
-}
-
-// TEX: the scene has textures (kernels are instantiated both ways so untextured scenes keep
-// the texture code out of their register budget).
-template <bool TEX>
-__device__ __forceinline__ void reconstruct(const DevScene& S, const Hit& h, f3 d, SurfaceHit& s) {
-    const int ti = h.tri;
-    const float4 A = S.isect[3 * ti];
-    const float4 S0 = S.shade[4 * ti], S1 = S.shade[4 * ti + 1], S2 = S.shade[4 * ti + 2], S3 = S.shade[4 * ti + 3];
-    // the edges again from the vertices: e = v - v0 is the one fp32 subtraction k_gather stored in
-    // isect, so Ng is bit-identical, and the hit costs five gathers instead of seven
-    const float4 E1 = make_float4(S0.x - A.x, S0.y - A.y, S0.z - A.z, 0.0f);
-    const float4 E2 = make_float4(S1.x - A.x, S1.y - A.y, S1.z - A.z, 0.0f);
-    const int mi = __float_as_int(S3.w);
-    const float4 M0 = S.mats[kMatStride * mi], M1 = S.mats[kMatStride * mi + 1];
-    f3 wo_w = normalize(-d);
-    f3 v0 = mk(A.x, A.y, A.z), v1 = mk(S0.x, S0.y, S0.z), v2 = mk(S1.x, S1.y, S1.z);
-    f3 n0 = mk(S0.w, S1.w, S2.x), n1 = mk(S2.y, S2.z, S2.w), n2 = mk(S3.x, S3.y, S3.z);
-    f3 Ng = cross(mk(E1.x, E1.y, E1.z), mk(E2.x, E2.y, E2.z));
-    const float u = h.u, v = h.v;
-    float w = 1.0f - u - v;
-    f3 Ns = mk(w * n0.x + u * n1.x + v * n2.x, w * n0.y + u * n1.y + v * n2.y, w * n0.z + u * n1.z + v * n2.z);
-    if (M1.y != kNormalNone) {  // has normals: normalize(modelMatrix * vec4(Ns, 0))
-        if (TEX && M1.y == kNormalObject) {  // mat4_mul_vec4's order, row by row
-            const float4 R0 = S.mats[kMatStride * mi + 3], R1 = S.mats[kMatStride * mi + 4],
-                         R2 = S.mats[kMatStride * mi + 5];
-            Ns = mk(mat_row_dir(R0, Ns), mat_row_dir(R1, Ns), mat_row_dir(R2, Ns));
-        }
-        Ns = normalize(Ns);
-    }
-    const bool ng_flip = dot(wo_w, Ng) < 0.0f;
-    if (ng_flip) Ng = -Ng;
-    Ng = normalize(Ng);
-    if (dot(Ng, Ns) < 0.0f) Ns = -Ns;
-    Ns = normalize(Ns);
-    if (h.back) {
-        Ns = Ns * -1.0f;
-        Ng = Ng * -1.0f;
-    }
-    s.pos = mk(w * v0.x + u * v1.x + v * v2.x, w * v0.y + u * v1.y + v * v2.y, w * v0.z + u * v1.z + v * v2.z);
-    s.ng = Ng;
-    s.ng_back = ng_flip != h.back;  // negation and normalize are exact in the sign
-    s.albedo = mk(M0.x, M0.y, M0.z);
-    s.metallic = M0.w;
-    s.roughness = M1.x;
-    if (TEX) {
-        const float4 M2 = S.mats[kMatStride * mi + 2];
-        if (M2.y != 0.0f) apply_textures(S, ti, u, v, M1, M2, s.albedo, s.metallic, s.roughness, Ns);
-    }
-    f3 c1 = cross(Ns, mk(0.0f, 0.0f, 1.0f));
-    f3 c2 = cross(Ns, mk(0.0f, 1.0f, 0.0f));
-    f3 T = (length(c1) > length(c2)) ? c1 : c2;
-    T = normalize(T);
-    s.fr.t = T;
-    s.fr.b = cross(T, Ns);
-    s.fr.n = Ns;
-    s.wo = to_local(s.fr, wo_w);
-}
-
-// Path state of one camera sample (RadianceRayData, RayData.h:5-21).
-struct PathState {
-    f3 o, d, beta, radiance;
-    uint32_t seed;
-    int bounce;
-    bool end;
-};
-
-__device__ __forceinline__ void path_start(PathState& p, f3 o, f3 d, uint32_t seed) {  // SamplePath :626-635
-    p.o = o;
-    p.d = d;
-    p.beta = mk(1.0f, 1.0f, 1.0f);
-    p.radiance = mk(0.0f, 0.0f, 0.0f);
-    p.seed = seed;
-    p.bounce = 0;
-    p.end = false;
-}
-
-// The reference's debug print of one bounce of the debug path (devicePrograms.cu:428-437:
-// position, albedo, shading and geometry normal, roughness, metallic, at bounceCounter), plus
-// the hit triangle's global index, the throughput entering the bounce and the radiance so far.
-// Record layout: ptamd.h pt_debug_bounce.
-__device__ __forceinline__ void debug_record(const DevLaunch& L, int bounce, int prim, const SurfaceHit& sf, f3 beta,
-                                             f3 radiance) {
-    if (bounce < 1 || bounce > kDebugMaxBounces) return;
-    float* r = L.debug + (size_t)(bounce - 1) * kDebugRecordFloats;
-    const float v[kDebugRecordFloats] = {__int_as_float(bounce), __int_as_float(prim),
-                                         sf.pos.x, sf.pos.y, sf.pos.z, sf.albedo.x, sf.albedo.y, sf.albedo.z,
-                                         sf.fr.n.x, sf.fr.n.y, sf.fr.n.z, sf.ng.x, sf.ng.y, sf.ng.z,
-                                         sf.roughness, sf.metallic, beta.x, beta.y, beta.z,
-                                         radiance.x, radiance.y, radiance.z};
-    for (int k = 0; k < kDebugRecordFloats; ++k) r[k] = v[k];
-}
-
-// loop test of SamplePath (devicePrograms.cu:646)
-__device__ __forceinline__ bool path_alive(const DevLaunch& L, const PathState& p) {
-    return !p.end && p.bounce < L.max_bounces && length(p.beta) > 0.00001f;
-}
-
-// One iteration of SamplePath's loop: TraceRadiance + __closesthit__radiance
-// (devicePrograms.cu:343-514) or __miss__radiance (:576-583).  Returns false on a miss.
-template <int MODE, bool STATS, int DEPTH, bool TEX>
-__device__ __forceinline__ void path_segment(const DevScene& S, const DevLaunch& L, PathState& p, int* stk,
-                                             int stride, TravStats& ts, bool debug_path) {
-    Hit h;
-    bool hit = traverse<false, STATS, DEPTH, TEX>(S, p.o, p.d, 0.0f, 100.0f, h, stk, stride, ts);
-    if (!hit) {
-        p.beta = mk(0, 0, 0);
-        p.bounce = 100;
-        return;
-    }
-    p.bounce++;
-    if (p.bounce > L.max_bounces) {
-        p.end = true;
-        return;
-    }
-    SurfaceHit sf;
-    reconstruct<TEX>(S, h, p.d, sf);
-    if (debug_path) debug_record(L, p.bounce, __float_as_int(S.isect[3 * h.tri].w), sf, p.beta, p.radiance);
-    const bool conductor = rnd(p.seed) < sf.metallic;  // :400
-    // NEE (:446-472), Lighting::GetRandomPointLight (LightMethods.h:25-40)
-    float P = 0.0f;
-    int li = 0;
-    if (L.n_lights == 1) {
-        P = 1.0f;
-    } else if (L.n_lights > 1) {
-        float r = rnd(p.seed);
-        li = (int)(r * (float)L.n_lights);
-        if (li >= L.n_lights) li = L.n_lights - 1;
-        P = 1.0f / (float)L.n_lights;
-    }
-    if (P > 0.0f) {
-        const DevLight lt = L.lights[li];
-        f3 lpos = mk(lt.px, lt.py, lt.pz);
-        f3 ldir = lpos - sf.pos;
-        f3 ldn = normalize(ldir);
-        f3 so = sf.pos + 1e-3f * sf.ng;
-        Hit sh;
-        bool occluded = traverse<true, STATS, DEPTH, TEX>(S, so, normalize(ldir), 0.0f, length(ldir), sh, stk, stride, ts);
-        f3 lds = to_local(sf.fr, ldn);
-        if (!occluded) {
-            f3 f = bsdf_f<MODE>(p.seed, sf.albedo, sf.roughness, conductor, sf.wo, lds);
-            float c = abs_dot(lds, mk(0.0f, 0.0f, 1.0f));
-            f3 spectrum = f * c;
-            if (!is_zero(spectrum)) {
-                f3 dd = sf.pos - lpos;
-                float d2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
-                f3 Li = mk(lt.cr, lt.cg, lt.cb) / d2;
-                p.radiance = p.radiance + ((p.beta * spectrum) * Li) / (P * 1.0f);
-            }
-        }
-    }
-    BSample bs;
-    // the last segment's sampled direction is never traced (SamplePath's loop test, :646):
-    // skipping the sample leaves every traced value unchanged
-    if (p.bounce >= L.max_bounces) {
-        p.end = true;
-        return;
-    }
-    if (!bsdf_sample<MODE>(p.seed, sf.albedo, sf.roughness, conductor, sf.wo, bs)) {
-        p.end = true;
-        return;
-    }
-    float ac = abs_dot(bs.dir, mk(0.0f, 0.0f, 1.0f));
-    p.beta = p.beta * mk(bs.color.x * ac / bs.pdf, bs.color.y * ac / bs.pdf, bs.color.z * ac / bs.pdf);
-    f3 off = 1e-3f * sf.ng;
-    if (dot(bs.dir, mk(0.0f, 0.0f, 1.0f)) < 0.0f) off = -off;
-    p.o = sf.pos + off;
-    p.d = normalize(to_world(sf.fr, bs.dir));
 }
 
 }  // namespace pt

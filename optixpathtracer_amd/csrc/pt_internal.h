@@ -4,11 +4,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "pt_device.h"
 
 namespace pt {
+
+// A run-time flag as a compile-time constant for a launcher: f(std::true_type{}) or
+// f(std::false_type{}), so a kernel's bool template arguments are written flag() in one launch.
+template <class F>
+auto with_flag(bool v, F f) {
+    return v ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // Scene triangle soup in ORIGINAL order (meshes concatenated), world space.
 struct BuildInput {

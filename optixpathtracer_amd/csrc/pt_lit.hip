@@ -3,7 +3,7 @@
 // occluder candidate of every cell the bits leave to the tracer (k_occ_build); and the skip table
 // (pt_skip.h) whenever the triangle records or the BVH change.
 #include "pt_internal.h"
-#include "pt_lit.h"
+#include "pt_shade.h"
 #include "pt_skip.h"
 
 namespace pt {
@@ -186,7 +186,10 @@ __global__ __launch_bounds__(kLitBlock) void k_occ_build(DevScene S, const uint3
         if (!(h > kLitDelta)) break;  // also NaN
         TravState st;
         TravStats ts;
-        trav_init(st, p + 1e-3f * ng, normalize(ldir), 0.0f, length(ldir));
+        f3 so, sdir;
+        float stmax;
+        shadow_ray(p, ng, ldir, so, sdir, stmax);  // the ray a shading kernel emits from there
+        trav_init(st, so, sdir, 0.0f, stmax);
         while (!trav_step<kRayClosest, false, kOccStack, false>(S, st, lds_stack + threadIdx.x, kLitBlock, lds_spill, ts)) {
         }
         if (st.h.tri >= 0 && st.h.tri < S.ntri && __float_as_int(S.isect[3 * st.h.tri + 2].w) == 0) cand = st.h.tri;

@@ -9,6 +9,7 @@
 // no per-spp HBM round trip of the 24.9 MB colour buffer.  The BVH4 traversal stack lives
 // in LDS (32 entries x 256 threads = 32 KB per workgroup).
 #include "pt_internal.h"
+#include "pt_shade.h"
 
 namespace pt {
 
@@ -23,29 +24,84 @@ constexpr int kStack = PT_MK_STACK;
 #define PT_MK_WAVES 1
 #endif
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+// Path state of one camera sample (RadianceRayData, RayData.h:5-21).
+struct PathState {
+    f3 o, d, beta, radiance;
+    uint32_t seed;
+    int bounce;
+    bool end;
+};
+
+__device__ __forceinline__ void path_start(PathState& p, f3 o, f3 d, uint32_t seed) {  // SamplePath :626-635
+    p.o = o;
+    p.d = d;
+    p.beta = mk(1.0f, 1.0f, 1.0f);
+    p.radiance = mk(0.0f, 0.0f, 0.0f);
+    p.seed = seed;
+    p.bounce = 0;
+    p.end = false;
 }
 
-template <bool STATS>
-__device__ __forceinline__ void flush_stats(const DevLaunch& L, uint32_t segs, const TravStats& ts, int lane) {
-    unsigned long long a = wave_sum((unsigned long long)segs);
-    if (STATS) {
-        unsigned long long b = wave_sum((unsigned long long)ts.nodes);
-        unsigned long long c = wave_sum((unsigned long long)ts.tris);
-        unsigned long long d = wave_sum((unsigned long long)ts.rays);
-        unsigned long long e = wave_sum((unsigned long long)ts.overflow);
-        unsigned long long g = wave_sum((unsigned long long)ts.retrace);
-        if (lane == 0 && L.counters) {
-            atomicAdd(&L.counters[kCtrNodes], b);
-            atomicAdd(&L.counters[kCtrTriTests], c);
-            atomicAdd(&L.counters[kCtrRays], d);
-            atomicAdd(&L.counters[kCtrStackOverflows], e);
-            atomicAdd(&L.counters[kCtrRetraces], g);
+// loop test of SamplePath (devicePrograms.cu:646)
+__device__ __forceinline__ bool path_alive(const DevLaunch& L, const PathState& p) {
+    return !p.end && p.bounce < L.max_bounces && length(p.beta) > 0.00001f;
+}
+
+// One iteration of SamplePath's loop: TraceRadiance + __closesthit__radiance
+// (devicePrograms.cu:343-514) or __miss__radiance (:576-583), in the steps of pt_shade.h.
+template <int MODE, bool STATS, int DEPTH, bool TEX>
+__device__ __forceinline__ void path_segment(const DevScene& S, const DevLaunch& L, PathState& p, int* stk,
+                                             int stride, TravStats& ts, bool debug_path) {
+    Hit h;
+    bool hit = traverse<kRayClosest, STATS, DEPTH, TEX>(S, p.o, p.d, 0.0f, 100.0f, h, stk, stride, ts);
+    if (!hit) {
+        p.beta = mk(0, 0, 0);
+        p.bounce = 100;
+        return;
+    }
+    p.bounce++;
+    if (p.bounce > L.max_bounces) {
+        p.end = true;
+        return;
+    }
+    SurfaceHit sf;
+    reconstruct<TEX>(S, h, p.d, sf);
+    if (debug_path) debug_record(L, p.bounce, __float_as_int(S.isect[3 * h.tri].w), sf, p.beta, p.radiance);
+    const bool conductor = rnd(p.seed) < sf.metallic;  // :400
+    int li;
+    const float P = pick_light(L, p.seed, li);
+    if (P > 0.0f) {  // NEE (:446-472)
+        const DevLight lt = L.lights[li];
+        f3 so, sdir;
+        float stmax;
+        shadow_ray(sf.pos, sf.ng, light_vec(lt, sf.pos), so, sdir, stmax);
+        Hit sh;
+        bool occluded = traverse<kRayAny, STATS, DEPTH, TEX>(S, so, sdir, 0.0f, stmax, sh, stk, stride, ts);
+        f3 lds = light_local(sf, lt);
+        if (!occluded) {
+            f3 f = bsdf_f<MODE>(p.seed, sf.albedo, sf.roughness, conductor, sf.wo, lds);
+            f3 spectrum = nee_spectrum(f, lds);
+            if (!is_zero(spectrum))
+                p.radiance = p.radiance + nee_contrib(p.beta, spectrum, lt, light_dist2(lt, sf.pos), P);
         }
     }
+    BSample bs;
+    // the last segment's sampled direction is never traced (SamplePath's loop test, :646):
+    // skipping the sample leaves every traced value unchanged
+    if (p.bounce >= L.max_bounces || !bsdf_sample<MODE>(p.seed, sf.albedo, sf.roughness, conductor, sf.wo, bs)) {
+        p.end = true;
+        return;
+    }
+    continue_path(sf, bs, p.beta, p.o, p.d, p.bounce, L.max_bounces);  // path_alive holds its loop test
+}
+
+// The wave's path segments (counted with or without STATS) and its traversal statistics.  A function
+// with the sum first: written out in the kernel, or summed after the flush, the same operations cost
+// the Conductor and Dielectric kernels 4 VGPRs and a wave per SIMD (profiles/shade_steps_isa.txt).
+template <bool STATS>
+__device__ __forceinline__ void flush_segments(const DevLaunch& L, uint32_t segs, const TravStats& ts, int lane) {
+    const unsigned long long a = wave_sum_u64(segs);
+    flush_trav_stats<STATS>(L.counters, ts);
     if (lane == 0 && L.counters) atomicAdd(&L.counters[kCtrSegments], a);
 }
 
@@ -89,7 +145,7 @@ __global__ __launch_bounds__(kBlock, PT_MK_WAVES) void k_render_mega(DevScene S,
         L.accum[idx + 1] = sy;
         L.accum[idx + 2] = sz;
     }
-    flush_stats<STATS>(L, segs, ts, lane);
+    flush_segments<STATS>(L, segs, ts, lane);
 }
 
 template <bool TEX>
@@ -116,17 +172,11 @@ __global__ __launch_bounds__(kBlock) void k_trace(DevScene S, const float* rays,
 template <int MODE>
 hipError_t launch_mega(const DevScene& S, const DevLaunch& L, bool stats, hipStream_t stream) {
     dim3 grid((unsigned)((L.width + 15) / 16), (unsigned)((L.height + 15) / 16));
-    const bool tex = S.texinfo != nullptr;
-    if (tex) {
-        if (stats)
-            hipLaunchKernelGGL((k_render_mega<MODE, true, true>), grid, dim3(kBlock), 0, stream, S, L);
-        else
-            hipLaunchKernelGGL((k_render_mega<MODE, false, true>), grid, dim3(kBlock), 0, stream, S, L);
-    } else if (stats) {
-        hipLaunchKernelGGL((k_render_mega<MODE, true, false>), grid, dim3(kBlock), 0, stream, S, L);
-    } else {
-        hipLaunchKernelGGL((k_render_mega<MODE, false, false>), grid, dim3(kBlock), 0, stream, S, L);
-    }
+    with_flag(S.texinfo != nullptr, [&](auto tx) {
+        with_flag(stats, [&](auto st) {
+            hipLaunchKernelGGL((k_render_mega<MODE, st(), tx()>), grid, dim3(kBlock), 0, stream, S, L);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -147,12 +197,10 @@ hipError_t launch_render(int kernel, int mode, bool stats, const DevScene& S, co
 hipError_t launch_trace(const DevScene& S, const float* d_rays, int n, int* d_prim, float* d_thit, float* d_u,
                         float* d_v, int* d_back, int any_hit, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    if (S.texinfo)
-        hipLaunchKernelGGL(k_trace<true>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, S, d_rays, n,
-                       d_prim, d_thit, d_u, d_v, d_back, any_hit);
-    else
-        hipLaunchKernelGGL(k_trace<false>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, S, d_rays, n,
-                       d_prim, d_thit, d_u, d_v, d_back, any_hit);
+    with_flag(S.texinfo != nullptr, [&](auto tx) {
+        hipLaunchKernelGGL(k_trace<tx()>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, S, d_rays,
+                           n, d_prim, d_thit, d_u, d_v, d_back, any_hit);
+    });
     return hipGetLastError();
 }
 

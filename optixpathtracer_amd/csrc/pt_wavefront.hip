@@ -33,7 +33,7 @@
 #include <unordered_map>
 
 #include "pt_internal.h"
-#include "pt_lit.h"
+#include "pt_shade.h"
 #include "pt_skip.h"
 
 namespace pt {
@@ -150,39 +150,6 @@ __device__ __forceinline__ float4 hit_record(const TriBatchLds* slot, int path) 
     float u, v, code;
     hit_slot_words(slot, u, v, code);
     return make_float4(__int_as_float(path), u, v, code);
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Traversal statistics of a wave into the renderer's counters (pt_device.h Counter).
-template <bool STATS>
-__device__ __forceinline__ void flush_trav_stats(unsigned long long* counters, const TravStats& ts) {
-    if (!STATS || !counters) return;
-    const unsigned long long a = wave_sum_u64(ts.nodes), c = wave_sum_u64(ts.tris), d = wave_sum_u64(ts.rays);
-    const unsigned long long e = wave_sum_u64(ts.overflow), r = wave_sum_u64(ts.retrace);
-    const unsigned long long l = wave_sum_u64(ts.lds_nodes), u = wave_sum_u64(ts.unocc);
-    const unsigned long long sk = wave_sum_u64(ts.skips);
-    if (lane_id() == 0) {  // the wave-schedule counts are kept by every lane alike: lane 0's
-        atomicAdd(&counters[kCtrNodes], a);
-        atomicAdd(&counters[kCtrTriTests], c);
-        atomicAdd(&counters[kCtrRays], d);
-        atomicAdd(&counters[kCtrStackOverflows], e);
-        atomicAdd(&counters[kCtrRetraces], r);
-        atomicAdd(&counters[kCtrWaveSteps], (unsigned long long)ts.steps);
-        atomicAdd(&counters[kCtrWaveActive], (unsigned long long)ts.active);
-        atomicAdd(&counters[kCtrWaveNodeSteps], (unsigned long long)ts.node_steps);
-        atomicAdd(&counters[kCtrWaveTriSteps], (unsigned long long)ts.tri_steps);
-        atomicAdd(&counters[kCtrWaveRefills], (unsigned long long)ts.refills);
-        atomicAdd(&counters[kCtrLdsNodes], l);
-        atomicAdd(&counters[kCtrNeeUnoccluded], u);
-        atomicAdd(&counters[kCtrSkipRays], sk);
-        for (int k = 0; k < 6; ++k) atomicAdd(&counters[kCtrCoh0 + k], (unsigned long long)ts.coh[k]);
-        atomicAdd(&counters[kCtrCohLanes], (unsigned long long)ts.coh_lanes);
-    }
 }
 
 // Per-bounce counters: queue length and shadow-queue length, each on its own 128-B line
@@ -702,40 +669,6 @@ __device__ __forceinline__ Hit decode_hit(float4 hv) {
     return h;
 }
 
-// light choice: Lighting::GetRandomPointLight (LightMethods.h:25-40)
-__device__ __forceinline__ float pick_light(const DevLaunch& L, uint32_t& seed, int& li) {
-    li = 0;
-    if (L.n_lights == 1) return 1.0f;
-    if (L.n_lights <= 0) return 0.0f;
-    float r = rnd(seed);
-    li = (int)(r * (float)L.n_lights);
-    if (li >= L.n_lights) li = L.n_lights - 1;
-    return 1.0f / (float)L.n_lights;
-}
-
-// continuation (devicePrograms.cu:501-509) + loop test of SamplePath (:646)
-__device__ __forceinline__ bool continue_path(const SurfaceHit& sf, const BSample& bs, f3& beta, f3& o, f3& d,
-                                              int next_bounce, int max_bounces) {
-    float ac = abs_dot(bs.dir, mk(0.0f, 0.0f, 1.0f));
-    beta = beta * mk(bs.color.x * ac / bs.pdf, bs.color.y * ac / bs.pdf, bs.color.z * ac / bs.pdf);
-    f3 off = 1e-3f * sf.ng;
-    if (dot(bs.dir, mk(0.0f, 0.0f, 1.0f)) < 0.0f) off = -off;
-    o = sf.pos + off;
-    d = normalize(to_world(sf.fr, bs.dir));
-    return next_bounce < max_bounces && length(beta) > 0.00001f;
-}
-
-// Lit table (pt_lit.h): the hit's cell (-1: a triangle without cells) and the (light, cell) bit.
-// A set bit answers the NEE visibility test of a hit whose shadow origin is offset to the light's
-// side, dot(l - p, Ng) > kLitDelta: unoccluded, no shadow ray.
-__device__ __forceinline__ int lit_cell(const DevLaunch& L, const Hit& h) {
-    const uint32_t w = L.lit_tri[h.tri];
-    const int k = lit_level(w);
-    return k == kLitNoCells ? -1 : (int)(lit_first(w) + lit_cell_index(k, h.u, h.v));
-}
-__device__ __forceinline__ bool lit_bit(const DevLaunch& L, int li, int cell) {
-    return (L.lit_bits[(size_t)li * L.lit_words + ((uint32_t)cell >> 5)] >> (cell & 31)) & 1u;
-}
 // Adds the block's table answers to pt_stats.lit_table_answers: every wave leaves its count in
 // lds[wave] before one of the block's barriers (lit_count_wave), thread 0 adds them up after it.
 __device__ __forceinline__ void lit_count_wave(bool answered, int* lds) {
@@ -816,16 +749,15 @@ __global__ __launch_bounds__(kBlockWF) void k_shadow0_setup(DevScene S, DevLaunc
         const int li = k / P1, p = k - li * P1;
         const Hit h = decode_hit(W.hit[p]);  // frame 0's copy (queue 0 is in path order)
         float4 so = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(k)), sd = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
-        if (h.tri >= 0) {  // same arithmetic as the shading kernels' shadow rays
+        if (h.tri >= 0) {
             const float4 c = W.ray_d[0][p];
             SurfaceHit sf;
             reconstruct<TEX>(S, h, mk(c.x, c.y, c.z), sf);
-            const DevLight lt = L.lights[li];
-            const f3 ldir = mk(lt.px, lt.py, lt.pz) - sf.pos;
-            const f3 o = sf.pos + 1e-3f * sf.ng;
-            const f3 d = normalize(ldir);
+            f3 o, d;
+            float tmax;
+            shadow_ray(sf.pos, sf.ng, light_vec(L.lights[li], sf.pos), o, d, tmax);
             so = make_float4(o.x, o.y, o.z, __int_as_float(k));
-            sd = make_float4(d.x, d.y, d.z, length(ldir));
+            sd = make_float4(d.x, d.y, d.z, tmax);
         }
         W.sh_o[k] = so;
         W.sh_d[k] = sd;
@@ -907,21 +839,16 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
                 const float P = pick_light(L, seed, li);
                 if (P > 0.0f) {
                     const DevLight lt = L.lights[li];
-                    f3 lpos = mk(lt.px, lt.py, lt.pz);
-                    f3 ldir = lpos - sf.pos;
-                    f3 ldn = normalize(ldir);
-                    f3 lds = to_local(sf.fr, ldn);
+                    const f3 ldir = light_vec(lt, sf.pos);
+                    f3 lds = light_local(sf, lt);
                     // f has no RNG side effects in these modes: evaluate before the shadow test
                     f3 f = bsdf_f<MODE>(seed, sf.albedo, sf.roughness, conductor, sf.wo, lds);
-                    f3 spectrum = f * abs_dot(lds, mk(0.0f, 0.0f, 1.0f));
+                    f3 spectrum = nee_spectrum(f, lds);
                     if (!is_zero(spectrum)) {
-                        f3 dd = sf.pos - lpos;
-                        float d2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
-                        f3 Li = mk(lt.cr, lt.cg, lt.cb) / d2;
-                        contrib = ((beta * spectrum) * Li) / (P * 1.0f);
+                        contrib = nee_contrib(beta, spectrum, lt, light_dist2(lt, sf.pos), P);
                         // the lit table: the same add k_trace_pair would make for the unoccluded ray, at
                         // the same place in the path's bounce order
-                        lit_answer = lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta && lit_bit(L, li, lit_c);
+                        lit_answer = lit_side(lit_c, ldir, sf) && lit_bit(L, li, lit_c);
                         if (vis0 || lit_answer) {  // the visibility is already known (bounce 0: per pixel and light)
                             if (lit_answer || W.vis[vis0_index(L, path, li)]) {
                                 const float4 l = shade0 ? l0 : W.L[path];
@@ -929,12 +856,10 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
                                 if (!shade0) W.L[path] = l0;
                             }
                         } else {
-                            so = sf.pos + 1e-3f * sf.ng;
-                            sdir = normalize(ldir);
-                            stmax = length(ldir);
+                            shadow_ray(sf.pos, sf.ng, ldir, so, sdir, stmax);
                             emit_shadow = true;
-                            if (kOcc && occ && lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta)
-                                occ_t = L.occ_tab[li * (int)L.lit_cells + lit_c];  // lands while the BSDF is sampled
+                            if (kOcc && occ && lit_side(lit_c, ldir, sf))
+                                occ_t = occ_entry(L, li, lit_c);  // lands while the BSDF is sampled
                         }
                     }
                 }
@@ -962,7 +887,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
             // VGPRs; one int (the entry, loaded there) carried across the extension-queue stores costs 2
             // (DESIGN.md §5 v61).
             // The origin is the one k_trace_pair will read: the continuation ray's where the record
-            // shares it (below), else so -- the same expression, and the same bits either way.
+            // shares it (below), else so.
             if (occ) {
                 bool answered = false;
                 if (occ_t >= 0) answered = occ_answers<TEX>(S, occ_t, (kShareOrigin && emit_next) ? o : so, sdir, stmax);
@@ -976,8 +901,8 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
         }
         if (emit_shadow) {
             // Lambert: a sampled direction is never below the surface (lambert_sample forces z >= 0),
-            // so the continuation ray starts at the shadow ray's origin (sf.pos + 1e-3 * Ng, the
-            // same expression): the shadow record names that ray (qi) instead of repeating origin
+            // so the continuation ray starts at the shadow ray's origin (continue_path's offset is
+            // shadow_ray's, pt_shade.h): the shadow record names that ray (qi) instead of repeating origin
             // and path, and k_trace_pair reads them from the extension queue.  -1: own sh_o record.
             const bool share = kShareOrigin && emit_next;
             if (!share) stqs(W.sh_o + si, make_float4(so.x, so.y, so.z, __int_as_float(path)));
@@ -1036,15 +961,11 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
             const float P = pick_light(L, seed, li);
             if (P > 0.0f) {
                 const DevLight lt = L.lights[li];
-                f3 lpos = mk(lt.px, lt.py, lt.pz);
-                f3 lds = to_local(sf.fr, normalize(lpos - sf.pos));
+                f3 lds = light_local(sf, lt);
                 f3 fv = bsdf_f<MODE>(seed, sf.albedo, sf.roughness, conductor, sf.wo, lds);
-                f3 spectrum = fv * abs_dot(lds, mk(0.0f, 0.0f, 1.0f));
+                f3 spectrum = nee_spectrum(fv, lds);
                 if (!is_zero(spectrum) && W.vis[vis0_index(L, path, li)]) {
-                    f3 dd = sf.pos - lpos;
-                    float d2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
-                    f3 Li = mk(lt.cr, lt.cg, lt.cb) / d2;
-                    f3 contrib = ((beta * spectrum) * Li) / (P * 1.0f);
+                    f3 contrib = nee_contrib(beta, spectrum, lt, light_dist2(lt, sf.pos), P);
                     l0 = make_float4(0.0f + contrib.x, 0.0f + contrib.y, 0.0f + contrib.z, 0.0f);
                 }
             }
@@ -1215,24 +1136,22 @@ __global__ __launch_bounds__(kBlockShA) void k_shade_a(DevScene S, DevLaunch L, 
             if (b + 1 < L.max_bounces) smp_bucket = bk;
             if (P > 0.0f) {
                 const DevLight lt = L.lights[li];
-                f3 ldir = mk(lt.px, lt.py, lt.pz) - sf.pos;
-                const f3 ln = normalize(ldir);  // k_shade_nee's light direction, the same bits
+                const f3 ldir = light_vec(lt, sf.pos);
+                const f3 lds = light_local(sf, lt);  // ahead of the branches that use its normalize
                 int nb = 0;  // conductor
                 if (MODE == kModeLayered || !conductor)
-                    nb = !same_hemisphere(sf.wo, to_local(sf.fr, ln)) ? kNeeCross : nee_layered_bucket(bk, sf.albedo);
+                    nb = !same_hemisphere(sf.wo, lds) ? kNeeCross : nee_layered_bucket(bk, sf.albedo);
                 // the lit table: known unoccluded, straight to the NEE queue like the bounce-0 table
-                lit_answer = lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta && lit_bit(L, li, lit_c);
+                lit_answer = lit_side(lit_c, ldir, sf) && lit_bit(L, li, lit_c);
                 if (vis0 || lit_answer) {
                     if (lit_answer || W.vis[vis0_index(L, path, li)]) nee_bucket = nb;
                 } else {
-                    so = sf.pos + 1e-3f * sf.ng;
-                    sdir = ln;
-                    stmax = length(ldir);
+                    shadow_ray(sf.pos, sf.ng, ldir, so, sdir, stmax);
                     code = i | (nb << kItemBits);
                     emit = true;
                     // an occluded item gets neither a shadow ray nor a NEE-queue entry
-                    if (occ && lit_c >= 0 && dot(ldir, sf.ng) > kLitDelta)
-                        occ_answer = occ_answers<TEX>(S, L.occ_tab[li * (int)L.lit_cells + lit_c], so, sdir, stmax);
+                    if (occ && lit_side(lit_c, ldir, sf))
+                        occ_answer = occ_answers<TEX>(S, occ_entry(L, li, lit_c), so, sdir, stmax);
                     if (occ_answer) emit = false;
                 }
             }
@@ -1402,21 +1321,16 @@ __global__ __launch_bounds__(kBlockShB, PT_SHB_WAVES) void k_shade_nee(DevScene 
     float d2;
     {
         const DevLight lt = L.lights[li];
-        const f3 lpos = mk(lt.px, lt.py, lt.pz);
-        lds = to_local(sf.fr, normalize(lpos - sf.pos));
-        const f3 dd = sf.pos - lpos;
-        d2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
+        lds = light_local(sf, lt);
+        d2 = light_dist2(lt, sf.pos);
     }
-    const float cosl = abs_dot(lds, mk(0.0f, 0.0f, 1.0f));
+    const float cosl = abs_dot(lds, mk(0.0f, 0.0f, 1.0f));  // nee_spectrum's factor, taken before the walk
     f3 f = bsdf_f<MODE, true>(seed, sf.albedo, sf.roughness, aux & 1, sf.wo, lds);
     f3 spectrum = f * cosl;
     const float4 bv = W.beta[path];
     const f3 beta = mk(bv.x, bv.y, bv.z);
     if (!is_zero(spectrum)) {
-        const float P = L.n_lights == 1 ? 1.0f : 1.0f / (float)L.n_lights;
-        const DevLight lt = L.lights[li];
-        f3 Li = mk(lt.cr, lt.cg, lt.cb) / d2;
-        f3 add = ((beta * spectrum) * Li) / (P * 1.0f);
+        const f3 add = nee_contrib(beta, spectrum, L.lights[li], d2, light_pdf(L));
         float4 l = W.L[path];
         W.L[path] = make_float4(l.x + add.x, l.y + add.y, l.z + add.z, 0.0f);
     }
@@ -1532,11 +1446,6 @@ dim3 occupancy_grid(K kernel, int cus, int block = kBlockTrace) {
     return dim3((unsigned)(per_cu * std::max(1, cus)));
 }
 
-// A run-time flag as a compile-time constant: f(std::true_type{}) or f(std::false_type{}).
-template <class F>
-auto with_flag(bool v, F f) {
-    return v ? f(std::true_type{}) : f(std::false_type{});
-}
 // The variant of a trace kernel for a launch: f(tex, stats, block) with std::bool_constant TEX and
 // STATS and std::integral_constant<int> kBlockTraceWide or kBlockTrace.
 template <class F>

@@ -65,7 +65,7 @@ def _dot(a, b):
 
 
 def _shadow_rays(v0, v1, v2, u, v, light, delta):
-    """The shading kernels' shadow ray (pt_wavefront.hip k_shade_fused, pt_device.h reconstruct) in
+    """The shading kernels' shadow ray (pt_wavefront.hip k_shade_fused, pt_shade.h reconstruct) in
     fp32: p = w v0 + u v1 + v v2, Ng = normalize(cross(v1 - v0, v2 - v0)) on the light's side, origin
     p + 1e-3 Ng, direction normalize(l - p), tmax = |l - p|.  Returns the rays and dot(l - p, Ng)."""
     u, v = u[:, None], v[:, None]
