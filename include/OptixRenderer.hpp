@@ -268,6 +268,39 @@ class OptixRendererT {
         check(pt_get_temporal_info(r_, &i), "pt_get_temporal_info");
         return i;
     }
+    // --- adaptive sampling (pt_render_adaptive): rounds of frames over the pixels of the 8x8 tiles
+    // whose estimated error is still above the threshold; the per-pixel mean to h_pixels (W*H vec3).
+    static pt_adaptive_options AdaptiveDefaults() {
+        pt_adaptive_options o;
+        o.struct_size = (uint32_t)sizeof o;
+        check(pt_adaptive_options_default(&o), "pt_adaptive_options_default");
+        return o;
+    }
+    template <class Vec3>
+    void RenderAdaptive(uint32_t first_frame_id, Vec3 h_pixels[], const pt_adaptive_options* options = nullptr) {
+        static_assert(sizeof(Vec3) == 3 * sizeof(float), "h_pixels must be glm::vec3-like");
+        check(pt_render_adaptive(r_, first_frame_id, options, reinterpret_cast<float*>(h_pixels)), "pt_render_adaptive");
+    }
+    // The samples each pixel took in the last RenderAdaptive: W*H counts, row 0 = bottom.
+    std::vector<uint32_t> AdaptiveSamples() {
+        std::vector<uint32_t> out((size_t)w_ * (size_t)h_);
+        check(pt_adaptive_download(r_, PT_ADAPTIVE_SAMPLES, out.data(), (int64_t)(out.size() * sizeof(uint32_t))),
+              "pt_adaptive_download");
+        return out;
+    }
+    pt_adaptive_info AdaptiveInfo() {
+        pt_adaptive_info i;
+        i.struct_size = (uint32_t)sizeof i;
+        check(pt_get_adaptive_info(r_, &i), "pt_get_adaptive_info");
+        return i;
+    }
+    // Filters the last RenderAdaptive's mean into h_pixels.
+    template <class Vec3>
+    void DenoiseAdaptive(Vec3 h_pixels[], const pt_denoise_options* options = nullptr) {
+        static_assert(sizeof(Vec3) == 3 * sizeof(float), "h_pixels must be glm::vec3-like");
+        check(pt_denoise(r_, PT_DENOISE_SRC_ADAPTIVE, nullptr, 1.0f, options, reinterpret_cast<float*>(h_pixels)),
+              "pt_denoise");
+    }
     pt_renderer* handle() { return r_; }
 
    private:

@@ -666,6 +666,64 @@ int pt_motion_channels(int32_t kind);
  * the last pt_denoise_temporal had motion_vectors on. */
 int pt_motion_download(pt_renderer* r, int32_t kind, void* host, int64_t bytes);
 
+/* ---- adaptive sampling ---------------------------------------------------
+ * pt_render_adaptive renders rounds of round_frames frames, each only for the pixels of the 8x8
+ * tiles (aligned to pixel (0, 0) at the bottom-left, clipped at the right and top edges) that have
+ * not stopped.  Per pixel it keeps the sample count n, the fp32 RGB sum (the accumulation buffer)
+ * and the fp64 sums S1, S2 of the samples' luminance Y = (0.2126 r + 0.7152 g) + 0.0722 b (fp32)
+ * and of Y * Y.  After a round, in fp64: m = S1 / n, v = max(S2 / n - m * m, 0) / n,
+ * e = sqrt(v) / max(m, luminance_floor) (max(a, b) = a < b ? b : a, so a NaN stays); a tile's
+ * error is the pairwise-tree sum of e over its pixels divided by their number.  A tile stops, for
+ * good, once its error <= threshold and its pixels hold >= min_samples samples; every tile stops at
+ * max_samples.  A pixel therefore holds the samples of frame ids first .. first + n - 1, added in
+ * frame order: its sum is bit for bit what pt_render_frames(first, n) leaves there.  Wavefront
+ * kernel, one device, fp32 accumulation into the library's own buffer; no band split. */
+typedef struct pt_adaptive_options {
+    uint32_t struct_size;
+    float threshold;       /* > 0 or == 0: mean relative standard error of a tile's pixels at which it stops */
+    int32_t min_samples;   /* >= 1, rounded up to a multiple of round_frames */
+    int32_t max_samples;   /* >= min_samples, rounded up likewise */
+    int32_t round_frames;  /* >= 2 */
+    float luminance_floor; /* > 0 */
+} pt_adaptive_options;
+/* Fills the defaults (0.05, 16, 1024, 16, 0.01) into the first o->struct_size bytes. */
+int pt_adaptive_options_default(pt_adaptive_options* o);
+/* Clears the sum (as pt_render_accumulate) and the adaptive state, renders until no tile is active,
+ * and, unless host_rgb_mean is NULL, downloads the per-pixel mean sum / n (W*H*3 floats).
+ * Synchronous: the host reads the active-pixel count after every round.  opt NULL = the defaults.
+ * PT_ERR_INVALID for an option outside the range given above, the megakernel (PT_KERNEL_MEGA), a
+ * multi-device renderer, pt_set_accum_fp64 on, a caller-owned accumulation buffer
+ * (pt_set_accum_device_buffer) or a debug pixel set; PT_ERR_STATE before the first pt_resize. */
+int pt_render_adaptive(pt_renderer* r, uint32_t first_frame_id, const pt_adaptive_options* opt, float* host_rgb_mean);
+#define PT_ADAPTIVE_SAMPLES 0     /* uint32 x 1 per pixel */
+#define PT_ADAPTIVE_ERROR 1       /* float x 1 per pixel: e of the last estimate the pixel took part in */
+#define PT_ADAPTIVE_MOMENTS 2     /* double x 2 per pixel: S1, S2 */
+#define PT_ADAPTIVE_TILE_ERROR 3  /* float x 1 per tile, tiles row-major from the bottom-left */
+#define PT_ADAPTIVE_TILE_ROUNDS 4 /* int32 x 1 per tile: rounds the tile was rendered in */
+/* Channels of a PT_ADAPTIVE_* kind (1, 1, 2, 1, 1); < 0 for a kind that does not exist. */
+int pt_adaptive_channels(int32_t kind);
+/* Copies state of the last pt_render_adaptive to host; bytes must be elements * channels * the
+ * element size above, with W * H elements for the per-pixel kinds and ceil(W / 8) * ceil(H / 8) for
+ * the per-tile ones.  PT_ERR_STATE without such a call since the last pt_resize or pt_accum_clear. */
+int pt_adaptive_download(pt_renderer* r, int32_t kind, void* host, int64_t bytes);
+/* The per-pixel mean of the last pt_render_adaptive on the device (W*H*3 floats); NULL without one. */
+float* pt_adaptive_mean_device_ptr(pt_renderer* r);
+typedef struct pt_adaptive_info {
+    uint32_t struct_size;
+    int32_t rounds;           /* of the last pt_render_adaptive */
+    int32_t tiles;
+    int32_t tiles_stopped;    /* tiles that met the threshold (the others ran to max_samples) */
+    uint64_t samples;         /* the sum of n over the pixels */
+    uint64_t samples_uniform; /* W * H * the largest n: what the same worst-case count costs on every pixel */
+    double render_ms;         /* wall time of the rounds' rendering, their waits included */
+    double estimate_ms;       /* HIP-event time of the error, compaction and resolve kernels */
+} pt_adaptive_info;
+/* Of the last pt_render_adaptive; zeros (and tiles of the present size) without one. */
+int pt_get_adaptive_info(pt_renderer* r, pt_adaptive_info* out);
+#define PT_DENOISE_SRC_ADAPTIVE 3 /* pt_denoise / pt_denoise_temporal source: the per-pixel mean of the last
+                                     pt_render_adaptive; PT_ERR_STATE without one, PT_ERR_INVALID unless
+                                     host_in is NULL */
+
 /* ---- glTF scene loading -----------------------------------------
  * ModelLoader::LoadModel (ModelLoading/ModelLoader.cpp:10-244): glTF 2.0 (.gltf with external
  * or data-URI buffers, or .glb) -> an owned pt_scene for pt_create.  One mesh per triangle

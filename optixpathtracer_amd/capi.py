@@ -171,7 +171,7 @@ class pt_lit_table_info(C.Structure):
 
 
 PT_AOV_ALBEDO, PT_AOV_NORMAL, PT_AOV_GEOM_NORMAL, PT_AOV_POSITION, PT_AOV_DEPTH, PT_AOV_PRIM, PT_AOV_ROUGH_METAL = range(7)
-PT_DENOISE_SRC_ACCUM, PT_DENOISE_SRC_DISPLAY, PT_DENOISE_SRC_HOST = range(3)
+PT_DENOISE_SRC_ACCUM, PT_DENOISE_SRC_DISPLAY, PT_DENOISE_SRC_HOST, PT_DENOISE_SRC_ADAPTIVE = range(4)
 
 AOV_KINDS = {
     "albedo": PT_AOV_ALBEDO,
@@ -225,6 +225,30 @@ MOTION_KINDS = {
     "prev_position": PT_MOTION_PREV_POSITION,
     "screen": PT_MOTION_SCREEN,
 }
+
+
+(PT_ADAPTIVE_SAMPLES, PT_ADAPTIVE_ERROR, PT_ADAPTIVE_MOMENTS, PT_ADAPTIVE_TILE_ERROR,
+ PT_ADAPTIVE_TILE_ROUNDS) = range(5)
+PT_ADAPTIVE_TILE = 8  # pixels along a tile's side
+
+ADAPTIVE_KINDS = {
+    "samples": PT_ADAPTIVE_SAMPLES,
+    "error": PT_ADAPTIVE_ERROR,
+    "moments": PT_ADAPTIVE_MOMENTS,
+    "tile_error": PT_ADAPTIVE_TILE_ERROR,
+    "tile_rounds": PT_ADAPTIVE_TILE_ROUNDS,
+}
+
+
+class pt_adaptive_options(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_float), ("min_samples", C.c_int32),
+                ("max_samples", C.c_int32), ("round_frames", C.c_int32), ("luminance_floor", C.c_float)]
+
+
+class pt_adaptive_info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("rounds", C.c_int32), ("tiles", C.c_int32),
+                ("tiles_stopped", C.c_int32), ("samples", C.c_uint64), ("samples_uniform", C.c_uint64),
+                ("render_ms", C.c_double), ("estimate_ms", C.c_double)]
 
 
 class _pt_launch_frame(C.Structure):
@@ -327,6 +351,12 @@ SIGNATURES = {
     "pt_get_temporal_info": (C.c_int, [_R, C.POINTER(pt_temporal_info)]),
     "pt_motion_channels": (C.c_int, [C.c_int32]),
     "pt_motion_download": (C.c_int, [_R, C.c_int32, C.c_void_p, C.c_int64]),
+    "pt_adaptive_options_default": (C.c_int, [C.POINTER(pt_adaptive_options)]),
+    "pt_render_adaptive": (C.c_int, [_R, C.c_uint32, C.POINTER(pt_adaptive_options), _FP]),
+    "pt_adaptive_channels": (C.c_int, [C.c_int32]),
+    "pt_adaptive_download": (C.c_int, [_R, C.c_int32, C.c_void_p, C.c_int64]),
+    "pt_adaptive_mean_device_ptr": (C.c_void_p, [_R]),
+    "pt_get_adaptive_info": (C.c_int, [_R, C.POINTER(pt_adaptive_info)]),
     "pt_model_load_gltf": (C.c_int, [C.c_char_p, pt_image_decode_fn, C.c_void_p, C.POINTER(_M)]),
     "pt_model_scene": (C.POINTER(pt_scene), [_M]),
     "pt_model_mesh_name": (C.c_char_p, [_M, C.c_int32]),

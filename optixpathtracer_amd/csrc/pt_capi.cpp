@@ -238,6 +238,7 @@ int pt_resize(pt_renderer* r, int32_t width, int32_t height) {
     r->d_display.reset();
     r->aov.release();
     r->temporal.release();
+    r->adaptive.release();
     r->multi.d_part.reset();
     r->d_accum64.reset();
     r->multi.d_part64.reset();
@@ -509,6 +510,7 @@ int pt_accum_clear(pt_renderer* r) {
     }
     PT_HIP(hipSetDevice(r->device), "hipSetDevice");
     size_t bytes = sizeof(float) * 3 * (size_t)r->width * (size_t)r->height;
+    r->adaptive.valid = false;  // the counts and moments described the sum that goes
     PT_HIP(hipMemsetAsync(r->accum(), 0, bytes, r->stream), "hipMemset accum");
     if (r->multi.d_part) PT_HIP(hipMemsetAsync(r->multi.d_part, 0, bytes, r->stream), "hipMemset partial sum");
     if (r->d_accum64) PT_HIP(hipMemsetAsync(r->d_accum64, 0, 2 * bytes, r->stream), "hipMemset fp64 accum");

@@ -87,9 +87,14 @@ int DenoiseCall::err(int code, const char* what) const { return fail(code, std::
 
 int DenoiseCall::check_source() const {
     if (!r) return err(PT_ERR_INVALID, "NULL renderer");
-    if (source != PT_DENOISE_SRC_ACCUM && source != PT_DENOISE_SRC_DISPLAY && source != PT_DENOISE_SRC_HOST)
+    if (source != PT_DENOISE_SRC_ACCUM && source != PT_DENOISE_SRC_DISPLAY && source != PT_DENOISE_SRC_HOST &&
+        source != PT_DENOISE_SRC_ADAPTIVE)
         return err(PT_ERR_INVALID, "no such source");
     if (source == PT_DENOISE_SRC_HOST && !host_in) return err(PT_ERR_INVALID, "NULL host_in");
+    // the newest source says which image it means: a host image beside it is a caller's mistake
+    // (the older device sources ignore host_in, and keep doing so)
+    if (source == PT_DENOISE_SRC_ADAPTIVE && host_in)
+        return err(PT_ERR_INVALID, "host_in must be NULL with the adaptive source");
     return PT_OK;
 }
 
@@ -106,6 +111,7 @@ int DenoiseCall::begin(bool reads_sigma_color) {
     if (!(o.albedo_floor > 0.0f)) return err(PT_ERR_INVALID, "albedo_floor must be > 0");
     if (r->width == 0) return err(PT_ERR_STATE, "call pt_resize first");
     if (source == PT_DENOISE_SRC_DISPLAY && !r->display_ready) return err(PT_ERR_STATE, "call pt_display_reset first");
+    if (source == PT_DENOISE_SRC_ADAPTIVE && !r->adaptive.valid) return err(PT_ERR_STATE, "call pt_render_adaptive first");
     PT_HIP(hipSetDevice(r->device), "hipSetDevice");
     pt_renderer::Aov& A = r->aov;
     n = (size_t)r->width * (size_t)r->height;
@@ -115,6 +121,7 @@ int DenoiseCall::begin(bool reads_sigma_color) {
         if (c.size() != n) PT_HIP(c.alloc(n), "hipMalloc filter colour");
     if (A.d_out.size() != 3 * n) PT_HIP(A.d_out.alloc(3 * n), "hipMalloc filter result");
     src = source == PT_DENOISE_SRC_ACCUM ? r->accum() : r->d_display.get();
+    if (source == PT_DENOISE_SRC_ADAPTIVE) src = r->adaptive.buf.mean;
     if (source == PT_DENOISE_SRC_HOST) {
         if (A.d_in.size() != 3 * n) PT_HIP(A.d_in.alloc(3 * n), "hipMalloc filter source");
         PT_HIP(hipMemcpyAsync(A.d_in, host_in, sizeof(float) * 3 * n, hipMemcpyHostToDevice, r->stream), "upload source");

@@ -39,6 +39,10 @@ DevLaunch make_launch(const pt_renderer* r, float* accum, uint32_t frame_base, u
     L.occ_tab = r->lit.active && r->occ.active ? r->occ.d_tab.get() : nullptr;
     L.lit_cells = r->lit.cells;
     L.skip_tab = r->skip.active ? r->skip.d_words.get() : nullptr;
+    L.pixel_map = nullptr;
+    L.n_pixels = r->width * r->height;
+    L.adapt_n = nullptr;
+    L.adapt_moments = nullptr;
     return L;
 }
 
@@ -85,8 +89,7 @@ struct WFPlan {
 
 // Queues for the plan's ns streams, nf_cap frames each; an allocation that fails for lack of
 // memory shrinks the plan (smaller batches on the first stream, fewer streams beyond it).
-int reserve_queues(pt_renderer* r, WFPlan* plan, size_t budget) {
-    const int P = r->width * r->height;
+int reserve_queues(pt_renderer* r, WFPlan* plan, size_t budget, int P) {
     const int maxb = std::max(1, r->max_bounces);
     int& nf_cap = plan->nf_cap;
     for (int k = 0; k < plan->ns; ++k) {
@@ -133,12 +136,12 @@ int reserve_queues(pt_renderer* r, WFPlan* plan, size_t budget) {
 }
 
 // The shape of a wavefront call of n frames: frames per batch, streams, bands, and the queues to
-// hold them (reserve_queues).
-int plan_wavefront(pt_renderer* r, uint32_t n, WFPlan* plan) {
+// hold them (reserve_queues).  P: the pixels of a frame of this call -- the image's, or a mapped
+// call's (its batches then hold P * frames paths, so fewer pixels mean fewer batches).
+int plan_wavefront(pt_renderer* r, uint32_t n, WFPlan* plan, int P, bool mapped) {
     // Frames per wavefront launch chain: the queues hold nf frames' paths (208 B each), at most
     // kMaxWFPaths of them.  Batching amortises launch gaps and the per-kernel SIMT tail:
     // Lambert 1080p 545 / 648 / 664 Msamples/s at 1 / 8 / 16 frames.
-    const int P = r->width * r->height;
     const int maxb = std::max(1, r->max_bounces);
     const int nf_full = std::max(1, std::min({r->frames_per_launch, (int)std::min<uint32_t>(n, 1u << 20),
                                               kMaxWFPaths / std::max(1, P)}));
@@ -162,7 +165,7 @@ int plan_wavefront(pt_renderer* r, uint32_t n, WFPlan* plan) {
     // moves the camera every frame gets): its rows split into two bands, one per stream, so
     // each band's kernels fill the other's SIMT tails.  Every pixel's path depends only on its
     // pixel and frame id, so the image is the same bit for bit.
-    const bool bands = n == 1 && r->band_split && r->height >= 16;  // both bands non-empty
+    const bool bands = n == 1 && r->band_split && r->height >= 16 && !mapped;  // both bands non-empty
     // auto: a second stream pays where one batch's shading fills the other's trace tails
     // (Conductor +0.6 %, Dielectric +4 % at 128 frames); Lambert, Default and Layered run as
     // fast on one stream with half the queue memory
@@ -192,7 +195,7 @@ int plan_wavefront(pt_renderer* r, uint32_t n, WFPlan* plan) {
     plan->nf_cap = nf_cap;
     plan->ns = ns;
     plan->bands = bands;
-    const int rc = reserve_queues(r, plan, budget);
+    const int rc = reserve_queues(r, plan, budget, P);
     if (rc != PT_OK) return rc;
     r->last_streams = plan->ns;
     r->last_batch = plan->nf_cap;
@@ -250,7 +253,7 @@ WFState batch_queues(pt_renderer* r, int sk, bool speculative, bool first_batch)
 // Enqueue the n frames of a wavefront call in the plan's batches, with their events, bands and
 // cancel words.
 int enqueue_wavefront(pt_renderer* r, const WFPlan& plan, float* accum, uint32_t first, uint32_t n, double* accum64,
-                      size_t frame_stride, bool speculative) {
+                      size_t frame_stride, bool speculative, const PixelMap* pixels) {
     int rc = PT_OK;
     const DevScene S = r->scene();
     // Lambert / Conductor / Dielectric: k_extend at bounce 0, then k_trace_pair per bounce
@@ -281,10 +284,17 @@ int enqueue_wavefront(pt_renderer* r, const WFPlan& plan, float* accum, uint32_t
         const int nf = (int)std::min<uint32_t>((uint32_t)nf_cap, n - f);
         DevLaunch L = make_launch(r, frame_stride ? accum + (size_t)f * frame_stride : accum, first + f,
                                   (uint32_t)nf, accum64, frame_stride);
+        if (pixels) {  // a mapped launch: these pixels of the whole image
+            L.pixel_map = pixels->map;
+            L.n_pixels = pixels->count;
+            L.adapt_n = pixels->n;
+            L.adapt_moments = pixels->moments;
+        }
         const int band = nband > 1 ? batch : 0;
         if (nband > 1) {  // rows [row0, row0 + height) of the frame; the sum buffers at the band
             L.row0 = band == 0 ? 0 : rows0;
             L.height = band == 0 ? rows0 : r->height - rows0;
+            L.n_pixels = L.width * L.height;
             const size_t off = 3 * (size_t)r->width * (size_t)L.row0;
             L.accum += off;
             if (L.accum64) L.accum64 += off;
@@ -356,7 +366,7 @@ namespace pt {
 // are summed at the next pt_synchronize / pt_get_stats / download (collect_pending).
 // frame_stride > 0 (wavefront only): frame first + j is written alone to accum + j * frame_stride.
 int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, double* accum64, size_t frame_stride,
-                  bool speculative) {
+                  bool speculative, const PixelMap* pixels) {
     int rc = PT_OK;
     // callers that never synchronise through the library (pt_stream interop, device sum buffers,
     // loops over pt_launch / pt_display_add_frame) would grow the event pools without bound:
@@ -377,15 +387,18 @@ int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, doub
         return fail(PT_ERR_INVALID, "fp64 accumulation (pt_set_accum_fp64) runs with the wavefront kernel");
     if (frame_stride && kernel != PT_KERNEL_WAVEFRONT)
         return fail(PT_ERR_INVALID, "per-frame images (render-ahead) run with the wavefront kernel");
+    if (pixels && (kernel != PT_KERNEL_WAVEFRONT || accum64 || frame_stride))
+        return fail(PT_ERR_INVALID, "mapped launches run with the wavefront kernel, into the fp32 sum");
     if (kernel == PT_KERNEL_WAVEFRONT) {
         WFPlan plan;
-        if ((rc = plan_wavefront(r, n, &plan)) != PT_OK) return rc;
-        rc = enqueue_wavefront(r, plan, accum, first, n, accum64, frame_stride, speculative);
+        const int P = pixels ? pixels->count : r->width * r->height;
+        if ((rc = plan_wavefront(r, n, &plan, P, pixels != nullptr)) != PT_OK) return rc;
+        rc = enqueue_wavefront(r, plan, accum, first, n, accum64, frame_stride, speculative, pixels);
     } else {
         rc = enqueue_megakernel(r, kernel, accum, first, n);
     }
     if (rc != PT_OK) return rc;
-    r->timing.samples += (uint64_t)n * (uint64_t)r->width * (uint64_t)r->height;
+    r->timing.samples += (uint64_t)n * (pixels ? (uint64_t)pixels->count : (uint64_t)r->width * (uint64_t)r->height);
     r->timing.calls++;
     return PT_OK;
 }

@@ -107,7 +107,21 @@ struct DevLaunch {
     // skip table (pt_skip.h): skip_tab[2 * triangle + side] = 0 or the BVH4 child link a continuation
     // ray leaving that side drops unvisited (fused wavefront modes); NULL = not in use
     const uint32_t* skip_tab;
+    // A mapped launch (pt_render_adaptive, pt_adaptive.hip) renders n_pixels pixels picked from the
+    // whole image: the launch's pixel p is image pixel pixel_map[p] (W*y + x; row0 = 0, height =
+    // image_height), and its frames add into the sum and the per-pixel moments through
+    // k_accum_adaptive.  NULL: the launch's pixels are the width * height of its band, n_pixels too.
+    const int* pixel_map;
+    int n_pixels;
+    uint32_t* adapt_n;     // mapped launches: per image pixel, the samples taken
+    double* adapt_moments; // ... and the fp64 sums of the samples' luminance and its square
 };
+// The pixels of a launch: the paths of one of its frames, and what p of path = frame * pixels + p counts.
+__device__ __forceinline__ int launch_pixels(const DevLaunch& L) { return L.n_pixels; }
+// The image pixel (W*y + x over the whole image) of the launch's pixel p.
+__device__ __forceinline__ int image_pixel(const DevLaunch& L, int p) {
+    return L.pixel_map ? L.pixel_map[p] : p + L.width * L.row0;
+}
 // Slots of DevLaunch::counters (pt_get_stats and pt_get_trace_coherence read them back).
 enum Counter : int {
     kCtrSegments = 0,    // path segments
@@ -146,7 +160,8 @@ constexpr int kDebugRecordFloats = 22;  // ptamd.h pt_debug_bounce
 // the launch's band), or -1.
 __device__ __forceinline__ int debug_path_id(const DevLaunch& L) {
     const uint32_t f = L.debug_frame - L.frame_base;
-    const int P = L.width * L.height, p = L.debug_pixel - L.width * L.row0;  // the band's pixel index
+    // the band's pixel index (a mapped launch has no debug pixel: pt_render_adaptive refuses one)
+    const int P = launch_pixels(L), p = L.debug_pixel - L.width * L.row0;
     return (L.debug_pixel >= 0 && p >= 0 && p < P && f < L.n_frames) ? (int)f * P + p : -1;
 }
 

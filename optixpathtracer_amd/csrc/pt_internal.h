@@ -249,4 +249,35 @@ hipError_t temporal_luminance_scale(const float4* cin, const float4* gn, float* 
 hipError_t temporal_atrous_iteration(const AtrousParams& A, const float* den, float4* hist, bool last, int lds_max_step,
                                      hipStream_t stream);
 
+// Adaptive sampling (pt_adaptive.hip).  AdaptiveBuffers: the image-sized state
+// (row 0 = bottom), the per-tile state (8x8 tiles from pixel (0, 0), row-major, clipped at the right
+// and top edges) and the list of the next round's pixels.
+constexpr int kTileActive = 1;   // rendered in the next round
+constexpr int kTileStopped = 0;  // its error met the threshold
+constexpr int kTileFull = 2;     // it holds max_samples samples
+struct AdaptiveBuffers {
+    int w, h, tiles_x, tiles_y;
+    uint32_t* n;       // samples per pixel
+    double* moments;   // S1, S2 per pixel
+    float* err;        // e per pixel, of the last estimate it took part in
+    float* tile_err;   // the same per tile
+    int* tile_rounds;  // rounds the tile was rendered in
+    int* tile_state;   // kTile*
+    int *tile_cnt, *tile_off;  // the compaction's counts and their exclusive scan
+    int* pixel_map;    // image pixels of the active tiles: tile ascending, raster order inside
+    int* count;        // its length
+    void* scan_tmp;    // hipCUB's scratch, scan_bytes of it (adaptive_scan_bytes)
+    size_t scan_bytes;
+};
+hipError_t adaptive_scan_bytes(int tiles, size_t* bytes);
+// A mapped launch's k_accum: radiance = the batch's WFState::L, L.n_pixels * nf records in path order.
+hipError_t accum_adaptive(const float4* radiance, const DevLaunch& L, int nf, hipStream_t stream);
+// After a round: e and the tile error of the tiles it rendered, their new state, then adaptive_compact.
+hipError_t adaptive_estimate(const AdaptiveBuffers& A, float threshold, uint32_t min_samples, uint32_t max_samples,
+                             float luminance_floor, hipStream_t stream);
+// pixel_map and count from tile_state.
+hipError_t adaptive_compact(const AdaptiveBuffers& A, hipStream_t stream);
+// mean[3 p ..] = sum[3 p ..] / (float)n[p]
+hipError_t adaptive_resolve(const float* sum, const uint32_t* n, float* mean, int pixels, hipStream_t stream);
+
 }  // namespace pt

@@ -201,4 +201,8 @@ PT_HD uint32_t f2u_sat(float f) {
     return (uint32_t)f;
 }
 
+// Rec. 709 luminance of an RGB record in this association order: the temporal filter's moments
+// (pt_temporal.hip) and the adaptive sampler's (pt_adaptive.hip) both mean exactly this.
+PT_HD float luminance(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+
 }  // namespace pt

@@ -1,6 +1,6 @@
 // pt_renderer.h — the renderer behind the C ABI (include/ptamd.h) and what the driver's translation
 // units share: pt_capi.cpp (entry points), pt_capi_bake.cpp, pt_capi_scene.cpp, pt_capi_launch.cpp,
-// pt_capi_ahead.cpp, pt_capi_tables.cpp, pt_capi_stats.cpp, pt_capi_denoise.cpp and pt_capi_temporal.cpp.  Not part of the public ABI.
+// pt_capi_ahead.cpp, pt_capi_tables.cpp, pt_capi_stats.cpp, pt_capi_denoise.cpp, pt_capi_temporal.cpp and pt_capi_adaptive.cpp.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -421,6 +421,21 @@ struct pt_renderer {
         }
     } temporal;
 
+    // adaptive sampling (pt_capi_adaptive.cpp, pt_adaptive.hip): the state of the last
+    // pt_render_adaptive and what pt_get_adaptive_info reports of it.  pt_resize frees the buffers,
+    // pt_accum_clear drops the state (the sum it describes is gone).
+    struct Adaptive {
+        pt::AdaptiveStore buf;
+        bool valid = false;  // buf holds a finished call's state, of the renderer's size
+        int rounds = 0;
+        double render_ms = 0.0, estimate_ms = 0.0;
+        pt::EventPool ev;  // around every round's estimate, and the resolve
+        void release() {
+            buf.release();
+            valid = false;
+        }
+    } adaptive;
+
     pt_renderer() = default;
     ~pt_renderer();  // the queue sets (wavefront_free); everything else releases itself
     pt::DevScene scene() const {
@@ -458,8 +473,15 @@ int commit_geometry(pt_renderer* r, int how);
 // pt_capi_launch.cpp
 size_t queue_bytes_held(const pt_renderer* r);
 size_t queue_budget_bytes(const pt_renderer* r);
+// What makes a launch a mapped one (DevLaunch::pixel_map): `count` image pixels and their adaptive state.
+struct PixelMap {
+    const int* map;
+    int count;
+    uint32_t* n;
+    double* moments;
+};
 int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, double* accum64 = nullptr,
-                  size_t frame_stride = 0, bool speculative = false);
+                  size_t frame_stride = 0, bool speculative = false, const PixelMap* pixels = nullptr);
 int render_frames_multi(pt_renderer* r, uint32_t first, uint32_t n);
 
 // pt_capi_ahead.cpp

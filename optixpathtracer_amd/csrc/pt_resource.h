@@ -48,6 +48,40 @@ public:
     }
 };
 
+// The adaptive sampler's device state (pt_render_adaptive, pt_internal.h AdaptiveBuffers): the
+// image-sized arrays, the per-tile ones, the next round's pixel list with its length, the per-pixel
+// mean and the scan's scratch.  All or none exist.
+struct AdaptiveStore {
+    DevBuf<uint32_t> n;
+    DevBuf<double> moments;
+    DevBuf<float> err, tile_err, mean;
+    DevBuf<int> tile_rounds, tile_state, tile_cnt, tile_off, pixel_map, count;
+    DevBuf<unsigned char> scan_tmp;
+    size_t pixels() const { return n.size(); }
+    size_t tiles() const { return tile_state.size(); }
+    hipError_t alloc(size_t pixels, size_t tiles, size_t scan_bytes) {
+        hipError_t e = moments.alloc(2 * pixels);
+        for (DevBuf<float>* b : {&err, &mean})
+            if (e == hipSuccess) e = b->alloc(b == &mean ? 3 * pixels : pixels);
+        if (e == hipSuccess) e = tile_err.alloc(tiles);
+        for (DevBuf<int>* b : {&tile_rounds, &tile_state, &tile_cnt, &tile_off})
+            if (e == hipSuccess) e = b->alloc(tiles);
+        if (e == hipSuccess) e = pixel_map.alloc(pixels);
+        if (e == hipSuccess) e = count.alloc(1);
+        if (e == hipSuccess) e = scan_tmp.alloc(std::max<size_t>(scan_bytes, 16));
+        if (e == hipSuccess) e = n.alloc(pixels);  // last: its size says that all of them exist
+        if (e != hipSuccess) release();
+        return e;
+    }
+    void release() {
+        n.reset();
+        moments.reset();
+        for (DevBuf<float>* b : {&err, &tile_err, &mean}) b->reset();
+        for (DevBuf<int>* b : {&tile_rounds, &tile_state, &tile_cnt, &tile_off, &pixel_map, &count}) b->reset();
+        scan_tmp.reset();
+    }
+};
+
 // One word of pinned host memory that kernels read over PCIe: `h` on the host, `d` the same word's
 // device address.
 struct PinnedWord {

@@ -25,7 +25,6 @@ namespace pt {
 
 namespace {
 
-__device__ __forceinline__ float luminance(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
 __device__ __forceinline__ float dot3(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ bool finite(float v) { return fabsf(v) <= 3.402823466e+38f; }
 

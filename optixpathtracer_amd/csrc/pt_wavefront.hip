@@ -340,13 +340,14 @@ constexpr int kItemBits = 28;  // a queue item index is < 2^28 (kMaxWFPaths); th
 // bounce-0 k_shade_fused derives the rest of the path state itself (shade0), so only frame 0's
 // rays are written -- the other frames' copies, throughputs and radiances are never read.
 __global__ __launch_bounds__(kBlockWF) void k_camera(WFState W, DevLaunch L, uint32_t frame0, int nf, int lean) {
-    const int P = L.width * L.height;
+    const int P = launch_pixels(L);
     const int Q = P * nf;
     if (wf_cancelled(W)) return;  // no barrier below; the queue count stays 0 if wave 0 of block 0 returns
     if (lean) {
         for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < P; q += gridDim.x * blockDim.x) {
             f3 o, d;
-            camera_ray(L, q % L.width, q / L.width, o, d);
+            const int ip = L.pixel_map ? L.pixel_map[q] : q;  // a mapped launch has row0 = 0: camera_ray's rows are the image's
+            camera_ray(L, ip % L.width, ip / L.width, o, d);
             W.ray_o[0][q] = make_float4(o.x, o.y, o.z, __int_as_float(q));
             W.ray_d[0][q] = make_float4(d.x, d.y, d.z, 0.0f);
         }
@@ -355,12 +356,13 @@ __global__ __launch_bounds__(kBlockWF) void k_camera(WFState W, DevLaunch L, uin
     }
     for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < Q; q += gridDim.x * blockDim.x) {
         const int f = q / P, p = q - f * P;
-        const int x = p % L.width, y = p / L.width;
+        const int ip = L.pixel_map ? L.pixel_map[p] : p;  // as above
+        const int x = ip % L.width, y = ip / L.width;
         f3 o, d;
         camera_ray(L, x, y, o, d);
         W.ray_o[0][q] = make_float4(o.x, o.y, o.z, __int_as_float(q));
         W.ray_d[0][q] = make_float4(d.x, d.y, d.z, 0.0f);
-        const uint32_t seed = tea16((uint32_t)(L.width * (y + L.row0) + x), frame0 + (uint32_t)f);  // devicePrograms.cu:631
+        const uint32_t seed = tea16((uint32_t)image_pixel(L, p), frame0 + (uint32_t)f);  // devicePrograms.cu:631
         W.beta[q] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(seed));
         W.L[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
@@ -735,13 +737,13 @@ __device__ __forceinline__ uint32_t skip_pick(uint2 w, const SurfaceHit& sf, boo
 // pixels + pixel], and the bounce-0 shading reads that table instead of tracing a shadow ray
 // per path.  Same rays, same any-hit answers: the images stay bit-identical.
 __device__ __forceinline__ int vis0_index(const DevLaunch& L, int path, int li) {
-    const int P1 = L.width * L.height;
+    const int P1 = launch_pixels(L);
     return li * P1 + path % P1;  // light-major (coherent shadow rays); path = frame * P1 + pixel
 }
 
 template <bool TEX>
 __global__ __launch_bounds__(kBlockWF) void k_shadow0_setup(DevScene S, DevLaunch L, WFState W) {
-    const int P1 = L.width * L.height;
+    const int P1 = launch_pixels(L);
     const int nl = L.n_lights;
     const int n = P1 * nl;
     if (wf_cancelled(W)) return;  // no barrier below
@@ -804,7 +806,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
         int path = 0;
         int occ_t = -1;  // the shadow ray's entry of the occluder table: -1 or a triangle
         uint32_t skip_w = 0;  // the continuation ray's skip word
-        const int P1 = L.width * L.height;
+        const int P1 = launch_pixels(L);
         float4 l0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // shade0: the path's radiance after bounce 0
         if (valid) {
             const float4 hv = ldqs(W.hit + i);
@@ -823,7 +825,7 @@ __global__ __launch_bounds__(shf_block(MODE), shf_waves(MODE)) void k_shade_fuse
                 SurfaceHit sf;
                 reconstruct<TEX>(S, h, d, sf);
                 if (shade0) {
-                    seed = tea16((uint32_t)(path % P1 + L.width * L.row0), L.frame_base + (uint32_t)(path / P1));
+                    seed = tea16((uint32_t)image_pixel(L, path % P1), L.frame_base + (uint32_t)(path / P1));
                     beta = mk(1.0f, 1.0f, 1.0f);
                 } else {
                     float4 bv = kBetaQ ? bv_q : ldqs(W.beta + path);
@@ -921,7 +923,7 @@ template <int MODE, bool TEX>
 __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S, DevLaunch L, WFState W, int nf) {
     constexpr bool kBetaQ = MODE == kModeLambert;  // as k_shade_fused
     constexpr int kBlock = shf_block(MODE), kWaves = kBlock / 64;
-    const int P1 = L.width * L.height;
+    const int P1 = launch_pixels(L);
     __shared__ int lds_q[kWaves + 1];
     if (blockIdx.x == 0 && threadIdx.x == 0 && L.counters)
         atomicAdd(&L.counters[kCtrShadeItems], (unsigned long long)P1 * (unsigned long long)nf);
@@ -944,6 +946,7 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
         }
     }
     const int dbg = debug_path_id(L);
+    const int ipix = valid ? image_pixel(L, p) : 0;
     float4* no = W.ray_o[1];
     float4* nd = W.ray_d[1];
     for (int f = 0; f < nf; ++f) {  // uniform trip count (block_append below)
@@ -954,7 +957,7 @@ __global__ __launch_bounds__(shf_block(MODE), 1) void k_shade0_pixel(DevScene S,
         float4 l0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         bool under = false;  // the continuation ray's origin is offset against sf.ng (skip_under)
         if (valid && tri >= 0) {
-            seed = tea16((uint32_t)(p + L.width * L.row0), L.frame_base + (uint32_t)f);  // devicePrograms.cu:631
+            seed = tea16((uint32_t)ipix, L.frame_base + (uint32_t)f);  // devicePrograms.cu:631
             if (path == dbg) debug_record(L, 1, __float_as_int(S.isect[3 * tri].w), sf, beta, mk(0.0f, 0.0f, 0.0f));
             const bool conductor = rnd(seed) < sf.metallic;  // :400
             int li;
@@ -1493,7 +1496,7 @@ hipError_t launch_shade(bool fused, const DevScene& S, const DevLaunch& L, const
 template <int MODE>
 hipError_t launch_shade0_pixel_t(const DevScene& S, const DevLaunch& L, const WFState& W, int nf, hipStream_t stream) {
     constexpr int block = shf_block(MODE);
-    const dim3 grid = item_grid(L.width * L.height, block);
+    const dim3 grid = item_grid(L.n_pixels, block);
     with_flag(S.texinfo != nullptr, [&](auto tx) {
         hipLaunchKernelGGL((k_shade0_pixel<MODE, tx()>), grid, dim3(block), 0, stream, S, L, W, nf);
     });
@@ -1581,7 +1584,7 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
                                   const hipEvent_t* trace_events, int* n_timed, hipEvent_t accum_wait,
                                   hipEvent_t accum_done, const hipEvent_t* shade_events, int* n_shade_timed,
                                   bool wide_trace) {
-    const int P = L.width * L.height * nf;  // paths in flight
+    const int P = L.n_pixels * nf;  // paths in flight
     const int maxb = L.max_bounces;
     hipError_t e = hipSuccess;
     if (W.cancel_seen && W.hold_release) {  // pt_set_debug_hold: the batch waits in k_hold first
@@ -1592,7 +1595,7 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
     if (e != hipSuccess) return e;
     // fused modes with the primary dedup: frame 0's camera rays only (k_camera `lean`, shade0)
     const bool lean = fused_mode(mode) && primary_dedup && nf > 1 && maxb > 0;
-    hipLaunchKernelGGL(k_camera, item_grid(lean ? L.width * L.height : P, kBlockWF), dim3(kBlockWF), 0, stream, W, L,
+    hipLaunchKernelGGL(k_camera, item_grid(lean ? L.n_pixels : P, kBlockWF), dim3(kBlockWF), 0, stream, W, L,
                        frame, nf, lean ? 1 : 0);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const bool fused = fused_mode(mode);
@@ -1650,7 +1653,7 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
     };
     // bounce-0 shadow dedup: one shadow ray per (pixel, light) instead of one per path; pays
     // off while the batch has at least as many frames as there are lights
-    const int P1 = L.width * L.height;
+    const int P1 = L.n_pixels;
     const int vis0 = (primary_dedup && nf > 1 && L.n_lights >= 1 && L.n_lights <= nf) ? L.n_lights : 0;
     auto shadow0 = [&]() -> hipError_t {
         if (!vis0) return hipSuccess;
@@ -1700,7 +1703,11 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
         }
     }
     if (accum_wait && (e = hipStreamWaitEvent(stream, accum_wait, 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_accum, item_grid(L.width * L.height, kBlockWF), dim3(kBlockWF), 0, stream, W, L, nf);
+    if (L.pixel_map) {
+        if ((e = accum_adaptive(W.L, L, nf, stream)) != hipSuccess) return e;
+    } else {
+        hipLaunchKernelGGL(k_accum, item_grid(L.width * L.height, kBlockWF), dim3(kBlockWF), 0, stream, W, L, nf);
+    }
     if (accum_done && (e = hipEventRecord(accum_done, stream)) != hipSuccess) return e;
     if (n_timed) *n_timed = timed;  // fused modes: max_bounces + 1; Default / Layered: max_bounces
     if (n_shade_timed) *n_shade_timed = stimed;  // max_bounces

@@ -285,8 +285,8 @@ class OptixRenderer:
 
     def denoise(self, source="accum", scale: float = 1.0, download: bool = True, **options):
         """pt_denoise: the a-trous filter over source * scale, guided by the G-buffer.  source:
-        "accum" (the sum buffer; scale = 1 / spp gives the mean), "display" (the progressive view)
-        or an (H, W, 3) array.  options: fields of pt_denoise_options (iterations, demodulate,
+        "accum" (the sum buffer; scale = 1 / spp gives the mean), "display" (the progressive view),
+        "adaptive" (the per-pixel mean of the last render_adaptive()) or an (H, W, 3) array.  options: fields of pt_denoise_options (iterations, demodulate,
         sigma_color, sigma_normal, sigma_position, albedo_floor); the rest keep their defaults.
         Returns the (H, W, 3) result; download=False leaves it on the device (pt_denoised_device_ptr,
         asynchronous) and returns None."""
@@ -300,9 +300,10 @@ class OptixRenderer:
         w, h = self.size
         host = None
         if isinstance(source, str):
-            srcs = {"accum": capi.PT_DENOISE_SRC_ACCUM, "display": capi.PT_DENOISE_SRC_DISPLAY}
+            srcs = {"accum": capi.PT_DENOISE_SRC_ACCUM, "display": capi.PT_DENOISE_SRC_DISPLAY,
+                    "adaptive": capi.PT_DENOISE_SRC_ADAPTIVE}
             if source not in srcs:
-                raise capi.PTError(f"denoise: source must be 'accum', 'display' or an array, not {source!r}",
+                raise capi.PTError(f"denoise: source must be 'accum', 'display', 'adaptive' or an array, not {source!r}",
                                    capi.PT_ERR_INVALID)
             src = srcs[source]
         else:
@@ -344,9 +345,10 @@ class OptixRenderer:
         w, h = self.size
         host = None
         if isinstance(source, str):
-            srcs = {"accum": capi.PT_DENOISE_SRC_ACCUM, "display": capi.PT_DENOISE_SRC_DISPLAY}
+            srcs = {"accum": capi.PT_DENOISE_SRC_ACCUM, "display": capi.PT_DENOISE_SRC_DISPLAY,
+                    "adaptive": capi.PT_DENOISE_SRC_ADAPTIVE}
             if source not in srcs:
-                raise capi.PTError(f"denoise_temporal: source must be 'accum', 'display' or an array, not {source!r}",
+                raise capi.PTError(f"denoise_temporal: source must be 'accum', 'display', 'adaptive' or an array, not {source!r}",
                                    capi.PT_ERR_INVALID)
             src = srcs[source]
         else:
@@ -397,6 +399,58 @@ class OptixRenderer:
         s.struct_size = C.sizeof(s)
         check(self.lib.pt_get_temporal_info(self.h, C.byref(s)), "pt_get_temporal_info")
         return {k: getattr(s, k) for k, _ in capi.pt_temporal_info._fields_ if k != "struct_size"}
+
+    # -- adaptive sampling ------------------------------------------------------------------------
+    def render_adaptive(self, first_frame_id: int = 1, download: bool = True, **options):
+        """pt_render_adaptive: clears the sum, then renders rounds of round_frames frames from
+        first_frame_id on, each only for the pixels of the 8x8 tiles whose mean relative standard
+        error is still above threshold.  options: fields of pt_adaptive_options
+        (threshold, min_samples, max_samples, round_frames, luminance_floor); the rest keep their
+        defaults.  Returns the (H, W, 3) per-pixel mean; download=False leaves it on the device
+        (pt_adaptive_mean_device_ptr) and returns None.  Synchronous."""
+        o = capi.pt_adaptive_options()
+        o.struct_size = C.sizeof(o)
+        check(self.lib.pt_adaptive_options_default(C.byref(o)), "pt_adaptive_options_default")
+        for k, v in options.items():
+            if k == "struct_size" or k not in dict(capi.pt_adaptive_options._fields_):
+                raise capi.PTError(f"render_adaptive: no such option {k!r}", capi.PT_ERR_INVALID)
+            setattr(o, k, v)
+        w, h = self.size
+        out = np.empty((h, w, 3), np.float32) if download else None
+        check(self.lib.pt_render_adaptive(self.h, int(first_frame_id), C.byref(o), fptr(out) if download else None),
+              "pt_render_adaptive")
+        return out
+
+    def adaptive_state(self, kind) -> np.ndarray:
+        """pt_adaptive_download: state of the last render_adaptive(), by name (capi.ADAPTIVE_KINDS) or
+        PT_ADAPTIVE_* value: (H, W) uint32 samples, (H, W) float32 error, (H, W, 2) float64 moments
+        (S1, S2), and per tile (rows of tiles from the bottom) float32 tile_error and int32
+        tile_rounds."""
+        k = capi.ADAPTIVE_KINDS[kind] if isinstance(kind, str) else int(kind)
+        ch = int(self.lib.pt_adaptive_channels(k))
+        if ch < 0:
+            raise capi.PTError(f"adaptive_state: no such kind {kind!r}", capi.PT_ERR_INVALID)
+        w, h = self.size
+        t = capi.PT_ADAPTIVE_TILE
+        shape, dtype = {
+            capi.PT_ADAPTIVE_SAMPLES: ((h, w), np.uint32),
+            capi.PT_ADAPTIVE_ERROR: ((h, w), np.float32),
+            capi.PT_ADAPTIVE_MOMENTS: ((h, w, 2), np.float64),
+            capi.PT_ADAPTIVE_TILE_ERROR: (((h + t - 1) // t, (w + t - 1) // t), np.float32),
+            capi.PT_ADAPTIVE_TILE_ROUNDS: (((h + t - 1) // t, (w + t - 1) // t), np.int32),
+        }[k]
+        out = np.empty(shape, dtype)
+        check(self.lib.pt_adaptive_download(self.h, k, out.ctypes.data, out.nbytes), "pt_adaptive_download")
+        return out
+
+    def adaptive_info(self) -> dict:
+        """pt_get_adaptive_info: of the last render_adaptive() the rounds, tiles and tiles_stopped (by
+        the threshold), the samples spent and what the largest count costs on every pixel
+        (samples_uniform), the wall time of the rounds and the device time of the estimates."""
+        s = capi.pt_adaptive_info()
+        s.struct_size = C.sizeof(s)
+        check(self.lib.pt_get_adaptive_info(self.h, C.byref(s)), "pt_get_adaptive_info")
+        return {k: getattr(s, k) for k, _ in capi.pt_adaptive_info._fields_ if k != "struct_size"}
 
     def accum_clear(self) -> None:
         check(self.lib.pt_accum_clear(self.h), "pt_accum_clear")
