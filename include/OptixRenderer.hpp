@@ -301,6 +301,20 @@ class OptixRendererT {
         check(pt_denoise(r_, PT_DENOISE_SRC_ADAPTIVE, nullptr, 1.0f, options, reinterpret_cast<float*>(h_pixels)),
               "pt_denoise");
     }
+    // --- anti-aliasing (pt_set_pixel_filter): frame F samples sub-pixel cell F mod supersample^2 of
+    // every pixel, and the frames are accumulated through the pixel filter `kind` (PT_FILTER_*);
+    // radius and param 0 take the kind's defaults.  Without arguments: pixel centres and the box.
+    void SetPixelFilter(int supersample = 1, int kind = PT_FILTER_BOX, float radius = 0.0f, float param = 0.0f) {
+        const pt_pixel_filter f = {(uint32_t)sizeof(pt_pixel_filter), supersample, kind, radius, param};
+        check(pt_set_pixel_filter(r_, &f), "pt_set_pixel_filter");
+    }
+    // The setting in force, radius and param resolved.
+    pt_pixel_filter PixelFilter() {
+        pt_pixel_filter f;
+        f.struct_size = (uint32_t)sizeof f;
+        check(pt_get_pixel_filter(r_, &f), "pt_get_pixel_filter");
+        return f;
+    }
     pt_renderer* handle() { return r_; }
 
    private:

@@ -724,6 +724,60 @@ int pt_get_adaptive_info(pt_renderer* r, pt_adaptive_info* out);
                                      pt_render_adaptive; PT_ERR_STATE without one, PT_ERR_INVALID unless
                                      host_in is NULL */
 
+/* ---- anti-aliasing: sub-pixel sampling and the pixel filter ----------------
+ * With supersample = s in {2, 4, 8}, output pixel (x, y) at frame F takes the path of pixel
+ * (s x + sx, s y + sy) of an image s times as large each way under the same camera, at frame F: its
+ * camera ray and its seed tea16(sW y' + x', F).  The cell (sx, sy) depends on F alone: with c =
+ * F mod s^2 and b = log2 s, sx is the top b bits of the 32-bit radical inverse of c and sy the top
+ * b bits of the second Sobol' dimension of c (direction numbers v0 = 2^31, v(k+1) = v(k) ^ (v(k) >> 1)),
+ * a permutation of the s^2 cells of which every aligned run of 4^k cell indices puts one sample in
+ * each cell of the 2^k x 2^k coarsening.  A frame still costs W * H paths.
+ * The sample of frame F sits at (ox, oy) = ((sx + 1/2) / s - 1/2, (sy + 1/2) / s - 1/2) from its
+ * pixel's centre.  A filter of 1-D profile f and radius r (in output pixels) has R = ceil(r - 1/2)
+ * in {0, 1, 2} and, per cell, the taps wx[i] = f(i + ox), i = -R..R, computed in fp64, divided by
+ * their sum and rounded to fp32; wy likewise from oy.  The filtered image of one frame is, in fp32
+ * without contraction,  g = 0;  for j = -R..R: for i = -R..R:
+ *     g = g + (wy[j] * wx[i]) * L_F(clamp(X + i, 0, W - 1), clamp(Y + j, 0, H - 1))
+ * (every tap is evaluated, so a sample that is not finite reaches its whole footprint), and the sum
+ * buffer stays "the sum of the n frames' images", added in frame order.  R = 0 is the plain sum.
+ *   f(t):  box       |t| <= r ? 1 : 0                                  (default r 0.5)
+ *          tent      max(0, 1 - |t| / r)                               (default r 1.0)
+ *          gaussian  max(0, exp(-t^2 / 2 sigma^2) - exp(-r^2 / 2 sigma^2)), sigma = param (default
+ *                    0.5)                                              (default r 1.5)
+ *          mitchell  Mitchell-Netravali at 2 t / r, B = param (default 1/3), C = (1 - B) / 2
+ *                                                                      (default r 2.0)
+ * The first-hit feature buffers (pt_aov_*) and with them the denoisers' guides stay at the pixel
+ * centre, whatever the setting.  Wavefront kernel, one device.  With supersample > 1 the primary
+ * dedup (pt_set_primary_dedup) is off: the frames of a batch no longer share their camera rays. */
+#define PT_FILTER_BOX 0
+#define PT_FILTER_TENT 1
+#define PT_FILTER_GAUSSIAN 2
+#define PT_FILTER_MITCHELL 3
+typedef struct pt_pixel_filter {
+    uint32_t struct_size;
+    int32_t supersample; /* 1 (off), 2, 4 or 8 */
+    int32_t kind;        /* PT_FILTER_* */
+    float radius;        /* 0 = the kind's default; else 0.5 <= radius <= 2.5 */
+    float param;         /* 0 = the kind's default; gaussian: sigma, mitchell: B */
+} pt_pixel_filter;
+/* Fills the defaults (1, PT_FILTER_BOX, 0, 0) into the first f->struct_size bytes. */
+int pt_pixel_filter_default(pt_pixel_filter* f);
+/* f NULL = the default.  Cancels a look-ahead batch in flight, as a camera change does; does not
+ * clear the sum.  PT_ERR_INVALID for a supersample, kind or radius outside the above, taps whose
+ * sum is not finite and positive, a multi-device renderer, or s^2 * W * H >= 2^31 (pt_resize refuses
+ * such a size likewise while a filter is set).  While a setting other than the default is in force,
+ * the render calls return PT_ERR_INVALID under the megakernel (PT_KERNEL_MEGA), and
+ * pt_render_adaptive does with R > 0 (supersample > 1 under the box is allowed).  A one-frame call
+ * with R > 0 does not split into row bands. */
+int pt_set_pixel_filter(pt_renderer* r, const pt_pixel_filter* f);
+/* The setting in force, radius and param resolved to the values in use. */
+int pt_get_pixel_filter(pt_renderer* r, pt_pixel_filter* f);
+/* Host only: xy[2 c], xy[2 c + 1] = (sx, sy) of cell index c, for c < supersample^2. */
+int pt_pixel_filter_cells(int32_t supersample, int32_t* xy);
+/* Host only: R of the filter and the 2 R + 1 taps along x and along y of cell index `cell`, exactly
+ * the words the device reads (wx, wy: room for 5 floats each; any of R, wx, wy may be NULL). */
+int pt_pixel_filter_taps(const pt_pixel_filter* f, int32_t cell, int32_t* R, float* wx, float* wy);
+
 /* ---- glTF scene loading -----------------------------------------
  * ModelLoader::LoadModel (ModelLoading/ModelLoader.cpp:10-244): glTF 2.0 (.gltf with external
  * or data-URI buffers, or .glb) -> an owned pt_scene for pt_create.  One mesh per triangle

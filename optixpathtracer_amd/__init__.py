@@ -5,7 +5,7 @@ host mirror of the reference's OptixRenderer interface.  See DESIGN.md.
 """
 from . import capi, scenes
 from .capi import MATERIAL_MODES, PTError
-from .renderer import OptixRenderer, camera_from_blender, setup_renderer
+from .renderer import OptixRenderer, camera_from_blender, pixel_filter_cells, pixel_filter_taps, setup_renderer
 
 __all__ = ["capi", "scenes", "OptixRenderer", "camera_from_blender", "setup_renderer", "PTError",
-           "MATERIAL_MODES"]
+           "MATERIAL_MODES", "pixel_filter_cells", "pixel_filter_taps"]

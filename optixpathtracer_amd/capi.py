@@ -251,6 +251,21 @@ class pt_adaptive_info(C.Structure):
                 ("render_ms", C.c_double), ("estimate_ms", C.c_double)]
 
 
+PT_FILTER_BOX, PT_FILTER_TENT, PT_FILTER_GAUSSIAN, PT_FILTER_MITCHELL = range(4)
+
+FILTER_KINDS = {
+    "box": PT_FILTER_BOX,
+    "tent": PT_FILTER_TENT,
+    "gaussian": PT_FILTER_GAUSSIAN,
+    "mitchell": PT_FILTER_MITCHELL,
+}
+
+
+class pt_pixel_filter(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("supersample", C.c_int32), ("kind", C.c_int32),
+                ("radius", C.c_float), ("param", C.c_float)]
+
+
 class _pt_launch_frame(C.Structure):
     _fields_ = [("color_buffer", C.c_void_p), ("size", C.c_int32 * 2), ("id", C.c_uint32)]
 
@@ -357,6 +372,11 @@ SIGNATURES = {
     "pt_adaptive_download": (C.c_int, [_R, C.c_int32, C.c_void_p, C.c_int64]),
     "pt_adaptive_mean_device_ptr": (C.c_void_p, [_R]),
     "pt_get_adaptive_info": (C.c_int, [_R, C.POINTER(pt_adaptive_info)]),
+    "pt_pixel_filter_default": (C.c_int, [C.POINTER(pt_pixel_filter)]),
+    "pt_set_pixel_filter": (C.c_int, [_R, C.POINTER(pt_pixel_filter)]),
+    "pt_get_pixel_filter": (C.c_int, [_R, C.POINTER(pt_pixel_filter)]),
+    "pt_pixel_filter_cells": (C.c_int, [C.c_int32, _IP]),
+    "pt_pixel_filter_taps": (C.c_int, [C.POINTER(pt_pixel_filter), C.c_int32, _IP, _FP, _FP]),
     "pt_model_load_gltf": (C.c_int, [C.c_char_p, pt_image_decode_fn, C.c_void_p, C.POINTER(_M)]),
     "pt_model_scene": (C.POINTER(pt_scene), [_M]),
     "pt_model_mesh_name": (C.c_char_p, [_M, C.c_int32]),

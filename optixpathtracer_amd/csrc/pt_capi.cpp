@@ -223,6 +223,8 @@ int pt_resize(pt_renderer* r, int32_t width, int32_t height) {
     if (!r) return fail(PT_ERR_INVALID, "pt_resize: NULL renderer");
     if (width < 0 || height < 0) return fail(PT_ERR_INVALID, "pt_resize: negative size");
     if (width == 0 || height == 0) return PT_OK;  // minimised window: no-op (OptixRenderer.cpp:651)
+    if (filter_image_too_large(r->filter.set.supersample, width, height))
+        return fail(PT_ERR_INVALID, "pt_resize: with the pixel filter set, supersample^2 * width * height must stay below 2^31");
     for (pt_renderer* p : r->multi.peers) {
         const int rc = pt_resize(p, width, height);
         if (rc) return rc;

@@ -91,6 +91,7 @@ int pt_render_adaptive(pt_renderer* r, uint32_t first_frame_id, const pt_adaptiv
     if (r->accum64) return fail(PT_ERR_INVALID, "pt_render_adaptive: not with fp64 accumulation (pt_set_accum_fp64)");
     if (r->user_accum) return fail(PT_ERR_INVALID, "pt_render_adaptive: not with a caller-owned accumulation buffer");
     if (r->debug_pixel >= 0) return fail(PT_ERR_INVALID, "pt_render_adaptive: not with a debug pixel set");
+    if (r->filter.R > 0) return fail(PT_ERR_INVALID, "pt_render_adaptive: not with a pixel filter wider than the box (pt_set_pixel_filter)");
     if (r->width == 0) return fail(PT_ERR_STATE, "pt_render_adaptive: call pt_resize first");
     const int R = o.round_frames;
     const uint32_t min_n = (uint32_t)round_up(o.min_samples, R), max_n = (uint32_t)round_up(o.max_samples, R);

@@ -19,6 +19,7 @@ static RenderKey render_key(const pt_renderer* r) {
     k.lights_version = r->lights_version;
     k.debug_version = r->debug_version;
     k.geom_version = r->geom.version;
+    k.filter_version = r->filter.version;
     k.lights = r->d_lights;
     std::memcpy(k.cam, r->cam_pos, sizeof r->cam_pos);
     std::memcpy(k.cam + 3, r->inv_view, sizeof r->inv_view);

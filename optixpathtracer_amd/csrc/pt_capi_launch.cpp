@@ -43,6 +43,10 @@ DevLaunch make_launch(const pt_renderer* r, float* accum, uint32_t frame_base, u
     L.n_pixels = r->width * r->height;
     L.adapt_n = nullptr;
     L.adapt_moments = nullptr;
+    L.ss_cells = r->filter.buf.cells;  // pt_set_pixel_filter: NULL without supersampling
+    L.ss = r->filter.set.supersample;
+    L.ss_taps = r->filter.buf.taps;  // NULL for a filter no wider than the box
+    L.ss_R = r->filter.R;
     return L;
 }
 
@@ -165,7 +169,8 @@ int plan_wavefront(pt_renderer* r, uint32_t n, WFPlan* plan, int P, bool mapped)
     // moves the camera every frame gets): its rows split into two bands, one per stream, so
     // each band's kernels fill the other's SIMT tails.  Every pixel's path depends only on its
     // pixel and frame id, so the image is the same bit for bit.
-    const bool bands = n == 1 && r->band_split && r->height >= 16 && !mapped;  // both bands non-empty
+    // A pixel filter wider than the box reads across the band edge: no bands, as for a mapped call.
+    const bool bands = n == 1 && r->band_split && r->height >= 16 && !mapped && r->filter.R == 0;  // both bands non-empty
     // auto: a second stream pays where one batch's shading fills the other's trace tails
     // (Conductor +0.6 %, Dielectric +4 % at 128 frames); Lambert, Default and Layered run as
     // fast on one stream with half the queue memory
@@ -314,8 +319,9 @@ int enqueue_wavefront(pt_renderer* r, const WFPlan& plan, float* accum, uint32_t
         // batches add into the sum in frame order; bands touch disjoint pixels
         const hipEvent_t accum_wait = dual && batch > 0 && nband == 1 ? r->ev_accum[(batch - 1) & 1].e : nullptr;
         const hipEvent_t accum_done = dual && nband == 1 ? r->ev_accum[batch & 1].e : nullptr;
+        // with sub-pixel cells the frames of a batch have their own camera rays: no primary dedup
         PT_HIP(launch_wavefront_frame(r->material_mode, r->trav_stats, S, L, wq, first + f,
-                                      nf, r->primary_dedup, dev_cus, st, tev, &n_timed,
+                                      nf, r->primary_dedup && !L.ss_cells, dev_cus, st, tev, &n_timed,
                                       accum_wait, accum_done, sev, &n_stimed, ns == 1 && r->wide_trace),
                "wavefront launch");
         if (tev) {  // pairs never recorded (the last ones handed out)
@@ -389,6 +395,14 @@ int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, doub
         return fail(PT_ERR_INVALID, "per-frame images (render-ahead) run with the wavefront kernel");
     if (pixels && (kernel != PT_KERNEL_WAVEFRONT || accum64 || frame_stride))
         return fail(PT_ERR_INVALID, "mapped launches run with the wavefront kernel, into the fp32 sum");
+    if (r->filter.active()) {  // pt_set_pixel_filter
+        if (kernel != PT_KERNEL_WAVEFRONT)
+            return fail(PT_ERR_INVALID, "a pixel filter (pt_set_pixel_filter) runs with the wavefront kernel, not the megakernel");
+        if (pixels && r->filter.R > 0)
+            return fail(PT_ERR_INVALID, "mapped launches take no pixel filter wider than the box");
+        if (filter_image_too_large(r->filter.set.supersample, r->width, r->height))
+            return fail(PT_ERR_INVALID, "pixel filter: supersample^2 * width * height must stay below 2^31");
+    }
     if (kernel == PT_KERNEL_WAVEFRONT) {
         WFPlan plan;
         const int P = pixels ? pixels->count : r->width * r->height;

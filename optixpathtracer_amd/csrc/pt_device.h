@@ -115,6 +115,14 @@ struct DevLaunch {
     int n_pixels;
     uint32_t* adapt_n;     // mapped launches: per image pixel, the samples taken
     double* adapt_moments; // ... and the fp64 sums of the samples' luminance and its square
+    // Pixel filter (pt_set_pixel_filter, pt_filter.hip).  ss_cells (NULL = off): frame F
+    // takes cell c = F mod ss^2, and the path of pixel (x, y) is that of pixel (ss x + ss_cells[2 c],
+    // ss y + ss_cells[2 c + 1]) of an image ss times as large each way (k_camera).  ss_taps (NULL = the
+    // box: plain k_accum): per cell the 2 ss_R + 1 weights along x, then those along y.
+    const int* ss_cells;
+    int ss;
+    const float* ss_taps;
+    int ss_R;
 };
 // The pixels of a launch: the paths of one of its frames, and what p of path = frame * pixels + p counts.
 __device__ __forceinline__ int launch_pixels(const DevLaunch& L) { return L.n_pixels; }
@@ -926,10 +934,11 @@ __device__ __forceinline__ bool traverse(const DevScene& S, f3 o, f3 d, float tm
     return s.h.tri >= 0;
 }
 
-// devicePrograms.cu:601-623 — pixel-centre primary ray (y: the launch's row, row0 + y the image's).
-__device__ __forceinline__ void camera_ray(const DevLaunch& L, int x, int y, f3& o, f3& d) {
-    float xs = ((float)x + 0.5f) / (float)L.width;
-    float ys = ((float)(y + L.row0) + 0.5f) / (float)L.image_height;
+// devicePrograms.cu:601-623 — the primary ray through the centre of pixel (x, y) of a w x h image
+// under L's camera (y: the image's row).
+__device__ __forceinline__ void camera_ray_at(const DevLaunch& L, int x, int y, int w, int h, f3& o, f3& d) {
+    float xs = ((float)x + 0.5f) / (float)w;
+    float ys = ((float)y + 0.5f) / (float)h;
     float ndc[4] = {xs * 2.0f - 1.0f, ys * 2.0f - 1.0f, 1.0f, 1.0f};
     float pv[4], pw[4];
     mat4_mul_vec4(L.inv_proj, ndc, pv);
@@ -939,6 +948,10 @@ __device__ __forceinline__ void camera_ray(const DevLaunch& L, int x, int y, f3&
     float inv = 1.0f / sqrtf(d4);
     d = mk(pw[0] * inv, pw[1] * inv, pw[2] * inv);
     o = mk(L.cam_pos[0], L.cam_pos[1], L.cam_pos[2]);
+}
+// Pixel-centre primary ray of the launch's own image (y: the launch's row, row0 + y the image's).
+__device__ __forceinline__ void camera_ray(const DevLaunch& L, int x, int y, f3& o, f3& d) {
+    camera_ray_at(L, x, y + L.row0, L.width, L.image_height, o, d);
 }
 
 }  // namespace pt

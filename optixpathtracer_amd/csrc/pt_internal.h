@@ -280,4 +280,11 @@ hipError_t adaptive_compact(const AdaptiveBuffers& A, hipStream_t stream);
 // mean[3 p ..] = sum[3 p ..] / (float)n[p]
 hipError_t adaptive_resolve(const float* sum, const uint32_t* n, float* mean, int pixels, hipStream_t stream);
 
+// Pixel filter (pt_filter.hip).  A filtered launch's k_accum: every frame's image is
+// gathered through the (2 L.ss_R + 1)^2 taps of the frame's cell (L.ss_taps) before it is added.
+// radiance = the batch's WFState::L, L.width * L.height * nf records in path order; L is a whole
+// image (row0 = 0, no pixel map), L.ss_R is 1 or 2.
+constexpr int kFilterMaxR = 2;
+hipError_t accum_filtered(const float4* radiance, const DevLaunch& L, int nf, hipStream_t stream);
+
 }  // namespace pt

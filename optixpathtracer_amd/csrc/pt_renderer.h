@@ -1,6 +1,6 @@
 // pt_renderer.h — the renderer behind the C ABI (include/ptamd.h) and what the driver's translation
 // units share: pt_capi.cpp (entry points), pt_capi_bake.cpp, pt_capi_scene.cpp, pt_capi_launch.cpp,
-// pt_capi_ahead.cpp, pt_capi_tables.cpp, pt_capi_stats.cpp, pt_capi_denoise.cpp, pt_capi_temporal.cpp and pt_capi_adaptive.cpp.  Not part of the public ABI.
+// pt_capi_ahead.cpp, pt_capi_tables.cpp, pt_capi_stats.cpp, pt_capi_denoise.cpp, pt_capi_temporal.cpp, pt_capi_adaptive.cpp and pt_capi_filter.cpp.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -85,14 +85,14 @@ struct StagedMesh {
 // Everything a 1-spp image depends on besides its frame id (render_key).
 struct RenderKey {
     int w = 0, h = 0, n_lights = 0, max_bounces = 0, mode = 0, kernel = 0, debug_pixel = -1;
-    uint32_t lights_version = 0, debug_frame = 0, debug_version = 0, geom_version = 0;
+    uint32_t lights_version = 0, debug_frame = 0, debug_version = 0, geom_version = 0, filter_version = 0;
     const void* lights = nullptr;
     float cam[3 + 16 + 16] = {};
     bool operator==(const RenderKey& o) const {
         return w == o.w && h == o.h && n_lights == o.n_lights && max_bounces == o.max_bounces && mode == o.mode &&
                kernel == o.kernel && debug_pixel == o.debug_pixel && lights_version == o.lights_version &&
                debug_frame == o.debug_frame && debug_version == o.debug_version && geom_version == o.geom_version &&
-               lights == o.lights &&
+               filter_version == o.filter_version && lights == o.lights &&
                std::memcmp(cam, o.cam, sizeof cam) == 0;
     }
 };
@@ -436,6 +436,17 @@ struct pt_renderer {
         }
     } adaptive;
 
+    // pixel filter (pt_capi_filter.cpp, pt_filter.hip): the setting with radius and param resolved,
+    // its tap radius R = ceil(radius - 1/2) and the tables the launches point at.  version is part of
+    // the render key: no ring frame rendered under another setting is served.
+    struct Filter {
+        pt_pixel_filter set = {(uint32_t)sizeof(pt_pixel_filter), 1, PT_FILTER_BOX, 0.5f, 0.0f};
+        int R = 0;
+        pt::FilterStore buf;
+        uint32_t version = 0;
+        bool active() const { return set.supersample > 1 || R > 0; }
+    } filter;
+
     pt_renderer() = default;
     ~pt_renderer();  // the queue sets (wavefront_free); everything else releases itself
     pt::DevScene scene() const {
@@ -551,6 +562,11 @@ struct DenoiseCall {
     int begin(bool reads_sigma_color);
     int finish(float* host_out) const;  // the download, unless host_out is NULL
 };
+
+// pt_capi_filter.cpp
+// Whether the supersampled image of a w x h frame has 2^31 pixels or more: its pixel index is the
+// path's seed and an int on the device.
+bool filter_image_too_large(int supersample, int64_t w, int64_t h);
 
 // pt_capi.cpp
 void mat4_inverse(const float* m, float* out);

@@ -82,6 +82,18 @@ struct AdaptiveStore {
     }
 };
 
+// The pixel filter's device tables (pt_set_pixel_filter, DevLaunch::ss_cells / ss_taps): the
+// sub-pixel cell of every cell index (x, y pairs; empty without supersampling) and the cells' tap
+// rows (empty for a filter no wider than the box).
+struct FilterStore {
+    DevBuf<int> cells;
+    DevBuf<float> taps;
+    void swap(FilterStore& o) noexcept {
+        cells.swap(o.cells);
+        taps.swap(o.taps);
+    }
+};
+
 // One word of pinned host memory that kernels read over PCIe: `h` on the host, `d` the same word's
 // device address.
 struct PinnedWord {

@@ -6,7 +6,8 @@
 // only a ray (low VGPR count -> high occupancy) and the BSDF code runs in its own kernel:
 //
 //   k_camera            : path q = f * P + pixel for the nf frames of the batch; camera ray ->
-//                         queue 0, state init
+//                         queue 0, state init (with sub-pixel cells, pt_set_pixel_filter: the ray and
+//                         the seed of the frame's cell of the pixel, DevLaunch::ss_cells)
 //   per bounce b:
 //     k_extend          : closest hit of queue b (BVH4 traversal, LDS stack) -> hit records
 //                         (fused modes: bounce 0 only; later bounces ride in k_trace_pair)
@@ -25,7 +26,8 @@
 //       k_shade_nee     : f (may draw), NEE, over the bucketed NEE queue
 //       k_shade_smp     : BSDF sample -> queue b+1, over the bucketed sample queue
 //   k_accum             : accum[pixel] += L[f * P + pixel] for f = 0 .. nf-1 in order (the same
-//                         fp32 order as the sequential reference accumulation)
+//                         fp32 order as the sequential reference accumulation); under a pixel filter
+//                         wider than the box, k_accum_filtered (pt_filter.hip) in its place
 //
 // Every kernel reads queue lengths from device memory written by an earlier launch (kernel
 // boundaries order the hand-off), so a whole batch of frames is enqueued without host round trips.
@@ -359,10 +361,19 @@ __global__ __launch_bounds__(kBlockWF) void k_camera(WFState W, DevLaunch L, uin
         const int ip = L.pixel_map ? L.pixel_map[p] : p;  // as above
         const int x = ip % L.width, y = ip / L.width;
         f3 o, d;
-        camera_ray(L, x, y, o, d);
+        uint32_t pixel;  // the seed's pixel index
+        if (L.ss_cells) {  // pt_set_pixel_filter: the frame's cell of this pixel, a pixel of the ss-fold image
+            const int* cell = L.ss_cells + 2 * ((frame0 + (uint32_t)f) & (uint32_t)(L.ss * L.ss - 1));
+            const int vx = L.ss * x + cell[0], vy = L.ss * (y + L.row0) + cell[1], vw = L.ss * L.width;
+            camera_ray_at(L, vx, vy, vw, L.ss * L.image_height, o, d);
+            pixel = (uint32_t)(vw * vy + vx);
+        } else {
+            camera_ray(L, x, y, o, d);
+            pixel = (uint32_t)image_pixel(L, p);
+        }
         W.ray_o[0][q] = make_float4(o.x, o.y, o.z, __int_as_float(q));
         W.ray_d[0][q] = make_float4(d.x, d.y, d.z, 0.0f);
-        const uint32_t seed = tea16((uint32_t)image_pixel(L, p), frame0 + (uint32_t)f);  // devicePrograms.cu:631
+        const uint32_t seed = tea16(pixel, frame0 + (uint32_t)f);  // devicePrograms.cu:631
         W.beta[q] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(seed));
         W.L[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
@@ -1705,6 +1716,8 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
     if (accum_wait && (e = hipStreamWaitEvent(stream, accum_wait, 0)) != hipSuccess) return e;
     if (L.pixel_map) {
         if ((e = accum_adaptive(W.L, L, nf, stream)) != hipSuccess) return e;
+    } else if (L.ss_taps) {  // a pixel filter wider than the box (pt_filter.hip)
+        if ((e = accum_filtered(W.L, L, nf, stream)) != hipSuccess) return e;
     } else {
         hipLaunchKernelGGL(k_accum, item_grid(L.width * L.height, kBlockWF), dim3(kBlockWF), 0, stream, W, L, nf);
     }

@@ -452,6 +452,24 @@ class OptixRenderer:
         check(self.lib.pt_get_adaptive_info(self.h, C.byref(s)), "pt_get_adaptive_info")
         return {k: getattr(s, k) for k, _ in capi.pt_adaptive_info._fields_ if k != "struct_size"}
 
+    # -- anti-aliasing ------------------------------------------------------------------------------
+    def set_pixel_filter(self, supersample: int = 1, kind="box", radius: float = 0.0, param: float = 0.0) -> None:
+        """pt_set_pixel_filter: frame F samples sub-pixel cell F mod supersample^2 of
+        every pixel (supersample 1, 2, 4 or 8), and the frames are accumulated through the pixel
+        filter `kind` ("box", "tent", "gaussian", "mitchell" or a PT_FILTER_* value); radius and
+        param 0 take the kind's defaults.  Without arguments: the default, pixel centres and the box.
+        The sum is not cleared."""
+        f = _pixel_filter(supersample, kind, radius, param, "set_pixel_filter")
+        check(self.lib.pt_set_pixel_filter(self.h, C.byref(f)), "pt_set_pixel_filter")
+
+    def pixel_filter(self) -> dict:
+        """pt_get_pixel_filter: supersample, kind (by name), and the radius and param in use."""
+        f = capi.pt_pixel_filter()
+        f.struct_size = C.sizeof(f)
+        check(self.lib.pt_get_pixel_filter(self.h, C.byref(f)), "pt_get_pixel_filter")
+        names = {v: k for k, v in capi.FILTER_KINDS.items()}
+        return {"supersample": f.supersample, "kind": names[f.kind], "radius": f.radius, "param": f.param}
+
     def accum_clear(self) -> None:
         check(self.lib.pt_accum_clear(self.h), "pt_accum_clear")
 
@@ -636,6 +654,38 @@ class OptixRenderer:
             self.close()
         except Exception:
             pass
+
+
+def _pixel_filter(supersample, kind, radius, param, what: str) -> "capi.pt_pixel_filter":
+    if isinstance(kind, str) and kind not in capi.FILTER_KINDS:
+        raise capi.PTError(f"{what}: kind must be one of {sorted(capi.FILTER_KINDS)}, not {kind!r}", capi.PT_ERR_INVALID)
+    f = capi.pt_pixel_filter()
+    f.struct_size = C.sizeof(f)
+    f.supersample = int(supersample)
+    f.kind = capi.FILTER_KINDS[kind] if isinstance(kind, str) else int(kind)
+    f.radius = float(radius)
+    f.param = float(param)
+    return f
+
+
+def pixel_filter_cells(supersample: int) -> np.ndarray:
+    """pt_pixel_filter_cells: (supersample^2, 2) int32, the sub-pixel cell (sx, sy) of every cell
+    index c = frame id mod supersample^2.  Host only."""
+    s = int(supersample)
+    out = np.zeros((max(1, s * s), 2), np.int32)
+    check(capi.load().pt_pixel_filter_cells(s, capi.iptr(out)), "pt_pixel_filter_cells")
+    return out
+
+
+def pixel_filter_taps(supersample: int = 1, kind="box", radius: float = 0.0, param: float = 0.0, cell: int = 0):
+    """pt_pixel_filter_taps: (R, wx, wy) of one cell index, the 2 R + 1 float32 weights along x and
+    along y exactly as the device reads them.  Host only."""
+    f = _pixel_filter(supersample, kind, radius, param, "pixel_filter_taps")
+    R = C.c_int32(0)
+    wx, wy = np.zeros(5, np.float32), np.zeros(5, np.float32)
+    check(capi.load().pt_pixel_filter_taps(C.byref(f), int(cell), C.byref(R), fptr(wx), fptr(wy)), "pt_pixel_filter_taps")
+    k = 2 * R.value + 1
+    return R.value, wx[:k].copy(), wy[:k].copy()
 
 
 def setup_renderer(scene: Scene, width: int, height: int, max_bounces: int, device: int = 0,
