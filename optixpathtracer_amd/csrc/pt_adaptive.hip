@@ -1,9 +1,8 @@
 // pt_adaptive.hip — the kernels of pt_render_adaptive (pt_capi_adaptive.cpp): rounds
-// of frames over the pixels of the 8x8 tiles that have not converged yet.
+// of frames over the pixels of the 8x8 tiles that have not converged yet.  A round's batches end in
+// the mapped accumulate, k_accum_adaptive (pt_accum.hip), which keeps the sum, the moments S1 and S2
+// and the sample counts; here are the estimate, the compaction and the resolve.
 //
-// k_accum_adaptive: k_accum for a mapped launch (DevLaunch::pixel_map).  One thread per mapped
-// pixel adds the batch's frames in frame order into the fp32 RGB sum, exactly as k_accum does, and
-// each frame's fp32 luminance, widened to fp64, into the pixel's moments S1 and S2.
 // k_adapt_error: one wave64 per tile, one lane per pixel (lane = 8 * row + column in the tile).  The
 // pixel's relative standard error e in fp64, then the tile's sum of e by a six-step butterfly: step k
 // adds the lanes whose index differs in bit k, so the tree is the same whatever the hardware does and
@@ -28,31 +27,6 @@ constexpr int kTile = 8;  // pixels along a tile's side: 64 pixels, one wave
 // a < b ? b : a -- a NaN in `a` stays (fmax would drop it), so a pixel whose moments are not finite
 // keeps its tile rendering
 __device__ __forceinline__ double max_keep_nan(double a, double b) { return a < b ? b : a; }
-
-__global__ __launch_bounds__(kBlockAd) void k_accum_adaptive(const float4* __restrict__ rad, DevLaunch L, int nf) {
-    const int P = launch_pixels(L);
-    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (p >= P) return;
-    const int ip = L.pixel_map[p];
-    const size_t idx = (size_t)ip * 3;
-    float sx = L.accum[idx], sy = L.accum[idx + 1], sz = L.accum[idx + 2];
-    double s1 = L.adapt_moments[2 * (size_t)ip], s2 = L.adapt_moments[2 * (size_t)ip + 1];
-    for (int f = 0; f < nf; ++f) {  // frames in order: the sequential accumulation
-        const float4 l = rad[(size_t)f * P + p];
-        sx += l.x;
-        sy += l.y;
-        sz += l.z;
-        const double y = (double)luminance(l);
-        s1 += y;
-        s2 += y * y;
-    }
-    L.accum[idx] = sx;
-    L.accum[idx + 1] = sy;
-    L.accum[idx + 2] = sz;
-    L.adapt_moments[2 * (size_t)ip] = s1;
-    L.adapt_moments[2 * (size_t)ip + 1] = s2;
-    L.adapt_n[ip] += (uint32_t)nf;
-}
 
 // This wave's tile and this lane's pixel of it: false when the wave is past the last tile.
 __device__ __forceinline__ bool wave_tile(const AdaptiveBuffers& A, int& tile, int& x, int& y) {
@@ -130,11 +104,6 @@ __global__ __launch_bounds__(kBlockAd) void k_adapt_resolve(const float* __restr
 inline dim3 grid_for(int items) { return dim3((unsigned)std::max(1, (items + kBlockAd - 1) / kBlockAd)); }
 
 }  // namespace
-
-hipError_t accum_adaptive(const float4* radiance, const DevLaunch& L, int nf, hipStream_t stream) {
-    hipLaunchKernelGGL(k_accum_adaptive, grid_for(L.n_pixels), dim3(kBlockAd), 0, stream, radiance, L, nf);
-    return hipGetLastError();
-}
 
 hipError_t adaptive_scan_bytes(int tiles, size_t* bytes) {
     *bytes = 0;

@@ -449,7 +449,11 @@ int pt_launch(pt_renderer* r, const pt_launch_params* lp) {
     if (r->lit.mode > 0) r->lit.version++;  // forced on: the array's contents may differ from call to call
     // colorBuffer[fbIndex] = pathRadiance (devicePrograms.cu:705): a one-frame sum into zeros
     hipError_t e = hipMemsetAsync(lp->frame.color_buffer, 0, sizeof(float) * 3 * (size_t)w * (size_t)h, r->stream);
-    int rc = e == hipSuccess ? launch_frames(r, lp->frame.color_buffer, lp->frame.id, 1)
+    FrameCall c;
+    c.first = lp->frame.id;
+    c.n = 1;
+    c.accum = lp->frame.color_buffer;
+    int rc = e == hipSuccess ? launch_frames(r, c)
                              : fail(PT_ERR_HIP, std::string("pt_launch: hipMemsetAsync: ") + hipGetErrorString(e));
     r->width = ow;
     r->height = oh;
@@ -525,9 +529,13 @@ int pt_render_frames(pt_renderer* r, uint32_t first_frame_id, uint32_t n_frames)
     if (r->width == 0) return fail(PT_ERR_STATE, "pt_render_frames: call pt_resize first");
     if (n_frames == 0) return PT_OK;
     PT_HIP(hipSetDevice(r->device), "hipSetDevice");
-    if (r->multi.comms.empty())
-        return launch_frames(r, r->accum(), first_frame_id, n_frames, r->accum64 ? r->d_accum64 : nullptr);
-    return render_frames_multi(r, first_frame_id, n_frames);
+    if (!r->multi.comms.empty()) return render_frames_multi(r, first_frame_id, n_frames);
+    FrameCall c;
+    c.first = first_frame_id;
+    c.n = n_frames;
+    c.accum = r->accum();
+    if (r->accum64) c.accum64 = r->d_accum64;
+    return launch_frames(r, c);
 }
 
 int pt_render_accumulate(pt_renderer* r, uint32_t spp, uint32_t first_frame_id, float* host_rgb_mean) {

@@ -113,7 +113,12 @@ int pt_render_adaptive(pt_renderer* r, uint32_t first_frame_id, const pt_adaptiv
         PT_HIP(hipStreamSynchronize(r->stream), "hipStreamSynchronize");
         if (active <= 0) break;
         const PixelMap pm = {A.pixel_map, active, A.n, A.moments};
-        if ((rc = launch_frames(r, r->accum(), first_frame_id + done, (uint32_t)R, nullptr, 0, false, &pm)) != PT_OK) return rc;
+        FrameCall c;
+        c.first = first_frame_id + done;
+        c.n = (uint32_t)R;
+        c.accum = r->accum();
+        c.pixels = &pm;
+        if ((rc = launch_frames(r, c)) != PT_OK) return rc;
         hipEvent_t a = nullptr, b = nullptr;
         PT_HIP(Ad.ev.next(&a, &b), "hipEventCreate");
         PT_HIP(hipEventRecord(a, r->stream), "hipEventRecord");

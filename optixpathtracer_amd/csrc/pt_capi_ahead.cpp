@@ -123,7 +123,13 @@ static int ring_fill(pt_renderer* r, int s, const RenderKey& k, uint32_t first, 
     sl.speculative = speculative && cancel_words(r);
     int rc = ring_reserve(r, s, std::max(n, cap), n3);
     if (rc == PT_OK) PT_HIP(hipEventRecord(sl.start, r->stream), "hipEventRecord");
-    if (rc == PT_OK) rc = launch_frames(r, sl.d, first, (uint32_t)n, nullptr, n3, sl.speculative);
+    FrameCall c;  // every frame its own image of the slot
+    c.first = first;
+    c.n = (uint32_t)n;
+    c.accum = sl.d;
+    c.frame_stride = n3;
+    c.speculative = sl.speculative;
+    if (rc == PT_OK) rc = launch_frames(r, c);
     if (rc != PT_OK) return rc;
     PT_HIP(hipEventRecord(sl.ready, r->stream), "hipEventRecord");
     sl.key = k;
@@ -248,7 +254,11 @@ int render_frame_image(pt_renderer* r, const float** img, hipEvent_t* ready, boo
         if (rc != PT_ERR_NOMEM) return rc;
     }
     PT_HIP(hipMemsetAsync(r->d_frame, 0, sizeof(float) * n3, r->stream), "hipMemset frame");
-    const int rc = launch_frames(r, r->d_frame, f, 1);
+    FrameCall c;
+    c.first = f;
+    c.n = 1;
+    c.accum = r->d_frame;
+    const int rc = launch_frames(r, c);
     if (rc) return rc;
     *img = r->d_frame;
     if (part_ready && r->band0_rows > 0) {  // the first band's rows are final once ev_band0 passes

@@ -1,6 +1,6 @@
 // pt_capi_filter.cpp — anti-aliasing (pt_set_pixel_filter): the sub-pixel cells, the
 // filters' tap tables and the setting.  The cells and taps are computed on the host and uploaded
-// once per setting; k_camera (pt_wavefront.hip) reads the cells, k_accum_filtered (pt_filter.hip)
+// once per setting; k_camera (pt_wavefront.hip) reads the cells, k_accum_filtered (pt_accum.hip)
 // the taps.
 #include "pt_renderer.h"
 

@@ -11,8 +11,15 @@ int next_event_pair(pt_renderer* r, hipEvent_t* a, hipEvent_t* b) {
     return PT_OK;
 }
 
-DevLaunch make_launch(const pt_renderer* r, float* accum, uint32_t frame_base, uint32_t n_frames,
-                      double* accum64 = nullptr, size_t frame_stride = 0) {
+// Rows [row0, row0 + rows) of the image, one band of a one-frame call; rows = 0: the whole image.
+struct RowBand {
+    int row0 = 0, rows = 0;
+};
+
+// The complete launch record of one batch of call c: its n_frames frames from frame id frame_base,
+// over the call's pixels or over one band of the image's rows.
+DevLaunch make_launch(const pt_renderer* r, const FrameCall& c, uint32_t frame_base, uint32_t n_frames,
+                      RowBand band = {}) {
     DevLaunch L;
     L.width = r->width;
     L.height = r->height;
@@ -26,9 +33,9 @@ DevLaunch make_launch(const pt_renderer* r, float* accum, uint32_t frame_base, u
     L.max_bounces = r->max_bounces;
     L.frame_base = frame_base;
     L.n_frames = n_frames;
-    L.accum = accum;
-    L.accum64 = accum64;
-    L.frame_stride = frame_stride;
+    L.accum = c.frame_stride ? c.accum + (size_t)(frame_base - c.first) * c.frame_stride : c.accum;
+    L.accum64 = c.accum64;
+    L.frame_stride = c.frame_stride;
     L.counters = r->d_counters;
     L.debug_pixel = r->d_debug ? r->debug_pixel : -1;
     L.debug_frame = r->debug_frame;
@@ -47,6 +54,20 @@ DevLaunch make_launch(const pt_renderer* r, float* accum, uint32_t frame_base, u
     L.ss = r->filter.set.supersample;
     L.ss_taps = r->filter.buf.taps;  // NULL for a filter no wider than the box
     L.ss_R = r->filter.R;
+    if (c.pixels) {  // a mapped launch: these pixels of the whole image
+        L.pixel_map = c.pixels->map;
+        L.n_pixels = c.pixels->count;
+        L.adapt_n = c.pixels->n;
+        L.adapt_moments = c.pixels->moments;
+    }
+    if (band.rows > 0) {  // rows [row0, row0 + height) of the frame; the sum buffers at the band
+        L.row0 = band.row0;
+        L.height = band.rows;
+        L.n_pixels = L.width * L.height;
+        const size_t off = 3 * (size_t)r->width * (size_t)L.row0;
+        L.accum += off;
+        if (L.accum64) L.accum64 += off;
+    }
     return L;
 }
 
@@ -223,23 +244,6 @@ int fork_resources(pt_renderer* r, int ns, int nband) {
     return PT_OK;
 }
 
-// pt_set_kernel_timing: the event pairs of one batch's trace and shading launches (null without).
-int timing_events(pt_renderer* r, bool fused, const hipEvent_t** tev, const hipEvent_t** sev) {
-    pt_renderer::Timing& t = r->timing;
-    *tev = *sev = nullptr;
-    if (!t.kernel_timing) return PT_OK;
-    t.tev_frame.resize(2 * (size_t)(r->max_bounces + 1));  // <= max_bounces + 1 trace launches
-    // launch 0 is the batch's k_extend; in the fused modes the others are k_trace_pair
-    for (int k = 0; k <= r->max_bounces; ++k)
-        PT_HIP((k > 0 && fused ? t.pev : t.tev).next(&t.tev_frame[2 * k], &t.tev_frame[2 * k + 1]), "hipEventCreate");
-    *tev = t.tev_frame.data();
-    t.sev_frame.resize(2 * (size_t)(r->max_bounces + 1));  // <= max_bounces shading launches
-    for (int k = 0; k <= r->max_bounces; ++k)
-        PT_HIP(t.sev.next(&t.sev_frame[2 * k], &t.sev_frame[2 * k + 1]), "hipEventCreate");
-    *sev = t.sev_frame.data();
-    return PT_OK;
-}
-
 // The queues of stream sk for one batch; a speculative batch also carries the cancel words.
 WFState batch_queues(pt_renderer* r, int sk, bool speculative, bool first_batch) {
     WFState wq = sk ? r->xwf[sk] : r->wf;
@@ -257,13 +261,9 @@ WFState batch_queues(pt_renderer* r, int sk, bool speculative, bool first_batch)
 
 // Enqueue the n frames of a wavefront call in the plan's batches, with their events, bands and
 // cancel words.
-int enqueue_wavefront(pt_renderer* r, const WFPlan& plan, float* accum, uint32_t first, uint32_t n, double* accum64,
-                      size_t frame_stride, bool speculative, const PixelMap* pixels) {
+int enqueue_wavefront(pt_renderer* r, const WFPlan& plan, const FrameCall& c) {
     int rc = PT_OK;
     const DevScene S = r->scene();
-    // Lambert / Conductor / Dielectric: k_extend at bounce 0, then k_trace_pair per bounce
-    const bool fused = r->material_mode == PT_MAT_LAMBERT || r->material_mode == PT_MAT_CONDUCTOR ||
-                       r->material_mode == PT_MAT_DIELECTRIC;
     const int ns = plan.ns, nf_cap = plan.nf_cap;
     const bool dual = ns > 1;
     const int nband = plan.bands && ns > 1 ? 2 : 1;  // row bands of a one-frame call
@@ -284,55 +284,36 @@ int enqueue_wavefront(pt_renderer* r, const WFPlan& plan, float* accum, uint32_t
     // download of its rows overlaps the rest of band 1
     const int rows0 = r->height * 7 / 16;
     r->band0_rows = nband > 1 ? rows0 : 0;
+    WFBatch B;
+    B.mode = r->material_mode;
+    B.stats = r->trav_stats;
+    B.wide_trace = ns == 1 && r->wide_trace;
+    B.cus = dev_cus;
+    pt_renderer::Timing& t = r->timing;
+    if (t.kernel_timing) B.timers = WFTimers{&t.tev, &t.pev, &t.sev};
     int batch = 0;
-    for (uint32_t f = 0; f < n; ++batch) {  // one event pair per batch (the batch's kernel chain)
-        const int nf = (int)std::min<uint32_t>((uint32_t)nf_cap, n - f);
-        DevLaunch L = make_launch(r, frame_stride ? accum + (size_t)f * frame_stride : accum, first + f,
-                                  (uint32_t)nf, accum64, frame_stride);
-        if (pixels) {  // a mapped launch: these pixels of the whole image
-            L.pixel_map = pixels->map;
-            L.n_pixels = pixels->count;
-            L.adapt_n = pixels->n;
-            L.adapt_moments = pixels->moments;
-        }
+    for (uint32_t f = 0; f < c.n; ++batch) {  // one event pair per batch (the batch's kernel chain)
+        const int nf = (int)std::min<uint32_t>((uint32_t)nf_cap, c.n - f);
         const int band = nband > 1 ? batch : 0;
-        if (nband > 1) {  // rows [row0, row0 + height) of the frame; the sum buffers at the band
-            L.row0 = band == 0 ? 0 : rows0;
-            L.height = band == 0 ? rows0 : r->height - rows0;
-            L.n_pixels = L.width * L.height;
-            const size_t off = 3 * (size_t)r->width * (size_t)L.row0;
-            L.accum += off;
-            if (L.accum64) L.accum64 += off;
-        }
+        RowBand rows;
+        if (nband > 1) rows = band == 0 ? RowBand{0, rows0} : RowBand{rows0, r->height - rows0};
+        const DevLaunch L = make_launch(r, c, c.first + f, (uint32_t)nf, rows);
         const int sk = batch % ns;  // stream of this batch
-        hipStream_t st = r->wf_stream(sk);
+        B.stream = r->wf_stream(sk);
         if (!dual) {
             rc = next_event_pair(r, &a, &b);
             if (rc) return rc;
+            PT_HIP(hipEventRecord(a, r->stream), "hipEventRecord");
         }
-        const hipEvent_t* tev = nullptr;
-        const hipEvent_t* sev = nullptr;
-        if ((rc = timing_events(r, fused, &tev, &sev)) != PT_OK) return rc;
-        if (!dual) PT_HIP(hipEventRecord(a, r->stream), "hipEventRecord");
-        int n_timed = 0, n_stimed = 0;
-        const WFState wq = batch_queues(r, sk, speculative, batch == 0);
+        const WFState wq = batch_queues(r, sk, c.speculative, batch == 0);
         // batches add into the sum in frame order; bands touch disjoint pixels
-        const hipEvent_t accum_wait = dual && batch > 0 && nband == 1 ? r->ev_accum[(batch - 1) & 1].e : nullptr;
-        const hipEvent_t accum_done = dual && nband == 1 ? r->ev_accum[batch & 1].e : nullptr;
+        B.accum_wait = dual && batch > 0 && nband == 1 ? r->ev_accum[(batch - 1) & 1].e : nullptr;
+        B.accum_done = dual && nband == 1 ? r->ev_accum[batch & 1].e : nullptr;
         // with sub-pixel cells the frames of a batch have their own camera rays: no primary dedup
-        PT_HIP(launch_wavefront_frame(r->material_mode, r->trav_stats, S, L, wq, first + f,
-                                      nf, r->primary_dedup && !L.ss_cells, dev_cus, st, tev, &n_timed,
-                                      accum_wait, accum_done, sev, &n_stimed, ns == 1 && r->wide_trace),
-               "wavefront launch");
-        if (tev) {  // pairs never recorded (the last ones handed out)
-            const int unused = r->max_bounces + 1 - n_timed;
-            const int unused_pair = fused ? std::min(unused, r->max_bounces) : 0;
-            r->timing.pev.give_back((size_t)unused_pair);
-            r->timing.tev.give_back((size_t)(unused - unused_pair));
-        }
-        if (sev) r->timing.sev.give_back((size_t)(r->max_bounces + 1 - n_stimed));
+        B.primary_dedup = r->primary_dedup && !L.ss_cells;
+        PT_HIP(launch_wavefront_batch(S, L, wq, B), "wavefront launch");
         if (!dual) PT_HIP(hipEventRecord(b, r->stream), "hipEventRecord");
-        if (nband > 1 && band == 0) PT_HIP(hipEventRecord(r->ev_band0, st), "hipEventRecord");
+        if (nband > 1 && band == 0) PT_HIP(hipEventRecord(r->ev_band0, B.stream), "hipEventRecord");
         if (band + 1 == nband) f += (uint32_t)nf;
     }
     if (dual) {
@@ -346,12 +327,12 @@ int enqueue_wavefront(pt_renderer* r, const WFPlan& plan, float* accum, uint32_t
 }
 
 // The megakernel: chunks of frames_per_launch frames on the library stream, one event pair each.
-int enqueue_megakernel(pt_renderer* r, int kernel, float* accum, uint32_t first, uint32_t n) {
+int enqueue_megakernel(pt_renderer* r, int kernel, const FrameCall& c) {
     const DevScene S = r->scene();
     const uint32_t chunk = (uint32_t)std::max(1, r->frames_per_launch);
-    for (uint32_t done = 0; done < n;) {
-        uint32_t k = std::min(chunk, n - done);
-        DevLaunch L = make_launch(r, accum, first + done, k);
+    for (uint32_t done = 0; done < c.n;) {
+        uint32_t k = std::min(chunk, c.n - done);
+        DevLaunch L = make_launch(r, c, c.first + done, k);
         hipEvent_t a, b;
         const int rc = next_event_pair(r, &a, &b);
         if (rc) return rc;
@@ -363,16 +344,34 @@ int enqueue_megakernel(pt_renderer* r, int kernel, float* accum, uint32_t first,
     return PT_OK;
 }
 
+// What launch_frames refuses: a destination form or a feature that the resolved kernel has no path for.
+int check_call(const pt_renderer* r, const FrameCall& c, int kernel) {
+    const bool wavefront = kernel == PT_KERNEL_WAVEFRONT;
+    if (c.accum64 && !wavefront)
+        return fail(PT_ERR_INVALID, "fp64 accumulation (pt_set_accum_fp64) runs with the wavefront kernel");
+    if (c.frame_stride && !wavefront)
+        return fail(PT_ERR_INVALID, "per-frame images (render-ahead) run with the wavefront kernel");
+    if (c.pixels && (!wavefront || c.accum64 || c.frame_stride))
+        return fail(PT_ERR_INVALID, "mapped launches run with the wavefront kernel, into the fp32 sum");
+    if (r->filter.active()) {  // pt_set_pixel_filter
+        if (!wavefront)
+            return fail(PT_ERR_INVALID, "a pixel filter (pt_set_pixel_filter) runs with the wavefront kernel, not the megakernel");
+        if (c.pixels && r->filter.R > 0)
+            return fail(PT_ERR_INVALID, "mapped launches take no pixel filter wider than the box");
+        if (filter_image_too_large(r->filter.set.supersample, r->width, r->height))
+            return fail(PT_ERR_INVALID, "pixel filter: supersample^2 * width * height must stay below 2^31");
+    }
+    return PT_OK;
+}
+
 }  // namespace
 
 namespace pt {
 
-// Launch frames [first, first+n) in chunks, adding into accum; brackets with events.  Does not
+// Launch the call's frames in chunks, adding into its destination; brackets with events.  Does not
 // wait for earlier work: the event pairs of every launch since the last synchronisation point
 // are summed at the next pt_synchronize / pt_get_stats / download (collect_pending).
-// frame_stride > 0 (wavefront only): frame first + j is written alone to accum + j * frame_stride.
-int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, double* accum64, size_t frame_stride,
-                  bool speculative, const PixelMap* pixels) {
+int launch_frames(pt_renderer* r, const FrameCall& c) {
     int rc = PT_OK;
     // callers that never synchronise through the library (pt_stream interop, device sum buffers,
     // loops over pt_launch / pt_display_add_frame) would grow the event pools without bound:
@@ -389,30 +388,17 @@ int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, doub
     // Dielectric 1239 / 758, Default 255 / 104).
     int kernel = r->kernel;
     if (kernel == PT_KERNEL_AUTO) kernel = PT_KERNEL_WAVEFRONT;
-    if (accum64 && kernel != PT_KERNEL_WAVEFRONT)
-        return fail(PT_ERR_INVALID, "fp64 accumulation (pt_set_accum_fp64) runs with the wavefront kernel");
-    if (frame_stride && kernel != PT_KERNEL_WAVEFRONT)
-        return fail(PT_ERR_INVALID, "per-frame images (render-ahead) run with the wavefront kernel");
-    if (pixels && (kernel != PT_KERNEL_WAVEFRONT || accum64 || frame_stride))
-        return fail(PT_ERR_INVALID, "mapped launches run with the wavefront kernel, into the fp32 sum");
-    if (r->filter.active()) {  // pt_set_pixel_filter
-        if (kernel != PT_KERNEL_WAVEFRONT)
-            return fail(PT_ERR_INVALID, "a pixel filter (pt_set_pixel_filter) runs with the wavefront kernel, not the megakernel");
-        if (pixels && r->filter.R > 0)
-            return fail(PT_ERR_INVALID, "mapped launches take no pixel filter wider than the box");
-        if (filter_image_too_large(r->filter.set.supersample, r->width, r->height))
-            return fail(PT_ERR_INVALID, "pixel filter: supersample^2 * width * height must stay below 2^31");
-    }
+    if ((rc = check_call(r, c, kernel)) != PT_OK) return rc;
+    const uint64_t P = c.pixels ? (uint64_t)c.pixels->count : (uint64_t)r->width * (uint64_t)r->height;
     if (kernel == PT_KERNEL_WAVEFRONT) {
         WFPlan plan;
-        const int P = pixels ? pixels->count : r->width * r->height;
-        if ((rc = plan_wavefront(r, n, &plan, P, pixels != nullptr)) != PT_OK) return rc;
-        rc = enqueue_wavefront(r, plan, accum, first, n, accum64, frame_stride, speculative, pixels);
+        if ((rc = plan_wavefront(r, c.n, &plan, (int)P, c.pixels != nullptr)) != PT_OK) return rc;
+        rc = enqueue_wavefront(r, plan, c);
     } else {
-        rc = enqueue_megakernel(r, kernel, accum, first, n);
+        rc = enqueue_megakernel(r, kernel, c);
     }
     if (rc != PT_OK) return rc;
-    r->timing.samples += (uint64_t)n * (pixels ? (uint64_t)pixels->count : (uint64_t)r->width * (uint64_t)r->height);
+    r->timing.samples += (uint64_t)c.n * P;
     r->timing.calls++;
     return PT_OK;
 }
@@ -433,8 +419,12 @@ int render_frames_multi(pt_renderer* r, uint32_t first, uint32_t n) {
         pt_renderer* d = g == 0 ? r : r->multi.peers[(size_t)g - 1];
         if (ng > 0) {
             PT_HIP(hipSetDevice(d->device), "hipSetDevice");
-            const int rc = launch_frames(d, g == 0 ? r->multi.d_part : d->accum(), f, ng,
-                                         r->accum64 ? (g == 0 ? r->multi.d_part64 : d->d_accum64) : nullptr);
+            FrameCall c;
+            c.first = f;
+            c.n = ng;
+            c.accum = g == 0 ? r->multi.d_part.get() : d->accum();
+            if (r->accum64) c.accum64 = g == 0 ? r->multi.d_part64.get() : d->d_accum64.get();
+            const int rc = launch_frames(d, c);
             if (rc) return rc;
         }
         f += ng;

@@ -107,7 +107,7 @@ struct DevLaunch {
     // skip table (pt_skip.h): skip_tab[2 * triangle + side] = 0 or the BVH4 child link a continuation
     // ray leaving that side drops unvisited (fused wavefront modes); NULL = not in use
     const uint32_t* skip_tab;
-    // A mapped launch (pt_render_adaptive, pt_adaptive.hip) renders n_pixels pixels picked from the
+    // A mapped launch (pt_render_adaptive, pt_accum.hip) renders n_pixels pixels picked from the
     // whole image: the launch's pixel p is image pixel pixel_map[p] (W*y + x; row0 = 0, height =
     // image_height), and its frames add into the sum and the per-pixel moments through
     // k_accum_adaptive.  NULL: the launch's pixels are the width * height of its band, n_pixels too.
@@ -115,7 +115,7 @@ struct DevLaunch {
     int n_pixels;
     uint32_t* adapt_n;     // mapped launches: per image pixel, the samples taken
     double* adapt_moments; // ... and the fp64 sums of the samples' luminance and its square
-    // Pixel filter (pt_set_pixel_filter, pt_filter.hip).  ss_cells (NULL = off): frame F
+    // Pixel filter (pt_set_pixel_filter, pt_accum.hip).  ss_cells (NULL = off): frame F
     // takes cell c = F mod ss^2, and the path of pixel (x, y) is that of pixel (ss x + ss_cells[2 c],
     // ss y + ss_cells[2 c + 1]) of an image ss times as large each way (k_camera).  ss_taps (NULL = the
     // box: plain k_accum): per cell the 2 ss_R + 1 weights along x, then those along y.

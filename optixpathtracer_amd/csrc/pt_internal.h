@@ -110,27 +110,45 @@ struct WFState {
     const unsigned* hold_release = nullptr;
 };
 size_t wavefront_bytes(int paths, int max_bounces);
-// sum32[i] = (float)sum64[i] (the multi-device fp64 reduce's result -> the fp32 sum buffer)
-hipError_t accum_f64_to_f32(const double* sum64, float* sum32, size_t n, hipStream_t stream);
 hipError_t wavefront_alloc(WFState& W, int paths, int max_bounces);
 void wavefront_free(WFState& W);
-// Enqueue one frame (all bounces) of the wavefront pipeline; adds the frame into L.accum.
-// trace_events (optional): up to 2 * (L.max_bounces + 1) events recorded around the trace
-// launches; *n_timed (optional) receives the number of event pairs recorded.  shade_events /
-// n_shade_timed: the same for the bounce's dominant shading kernel (k_shade_fused / k_shade0_pixel
-// in the fused modes, k_shade_nee in Default / Layered), up to 2 * L.max_bounces events.
-// nf frames (frame .. frame + nf - 1) are traced together; W must hold nf * W * H paths.
-// primary_dedup: trace the batch's identical camera rays once per pixel (k_extend `dup`).
-// accum_wait / accum_done (optional): the batch's k_accum waits for accum_wait and records
-// accum_done, so batches on different streams still add into the sum in frame order.
-// wide_trace: the call runs on one stream, so the trace kernels take the wide
-// workgroups (pt_wavefront.hip kBlockTraceWide).
-hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const DevLaunch& L, const WFState& W,
-                                  uint32_t frame, int nf, bool primary_dedup, int cus, hipStream_t stream,
-                                  const hipEvent_t* trace_events,
-                                  int* n_timed = nullptr, hipEvent_t accum_wait = nullptr,
-                                  hipEvent_t accum_done = nullptr, const hipEvent_t* shade_events = nullptr,
-                                  int* n_shade_timed = nullptr, bool wide_trace = false);
+// pt_set_kernel_timing: the pools whose event pairs bracket a batch's k_extend launches, its
+// k_trace_pair launches and the dominant shading launch of each bounce (k_shade_fused / k_shade0_pixel
+// in the fused modes, k_shade_nee in Default / Layered).  The launcher draws a pair at the launch it
+// brackets.  Null: not timed.
+struct EventPool;  // pt_resource.h
+struct WFTimers {
+    EventPool* extend = nullptr;
+    EventPool* pair = nullptr;
+    EventPool* shade = nullptr;
+};
+// What a wavefront batch needs besides its DevLaunch and its queues.
+struct WFBatch {
+    int mode = 0;                // material mode (kMode*)
+    bool stats = false;          // the trace kernels' STATS variants
+    bool primary_dedup = false;  // trace the batch's identical camera rays once per pixel (k_extend `dup`)
+    bool wide_trace = false;     // the call runs on one stream, so the trace kernels take the wide
+                                 // workgroups (pt_wavefront.hip kBlockTraceWide)
+    int cus = 0;                 // compute units of the device: the trace kernels' grids
+    hipStream_t stream = nullptr;
+    // optional: the batch's accumulate waits for accum_wait and records accum_done, so batches on
+    // different streams still add into the sum in frame order
+    hipEvent_t accum_wait = nullptr, accum_done = nullptr;
+    WFTimers timers;
+};
+// Enqueue one batch (all bounces) of the wavefront pipeline: the L.n_frames frames from L.frame_base
+// are traced together and added to L's destination (accum_batch); W must hold n_frames * n_pixels paths.
+hipError_t launch_wavefront_batch(const DevScene& S, const DevLaunch& L, const WFState& W, const WFBatch& B);
+// The accumulate stage (pt_accum.hip): adds the nf frames of `radiance` (the batch's WFState::L, nf
+// records per launch pixel in path order) to L's destination in frame order.  L.pixel_map: the mapped
+// kernel, into the fp32 sum and the adaptive moments (no accum64, no frame_stride).  L.ss_taps: every
+// frame's image gathered through the (2 L.ss_R + 1)^2 taps of the frame's cell first (DESIGN.md §13;
+// a whole image: row0 = 0 and no pixel map, L.ss_R from 1 to kFilterMaxR).  Else the plain kernel.
+// hipErrorInvalidValue where a combination has no kernel.
+constexpr int kFilterMaxR = 2;
+hipError_t accum_batch(const float4* radiance, const DevLaunch& L, int nf, hipStream_t stream);
+// sum32[i] = (float)sum64[i] (the multi-device fp64 reduce's result -> the fp32 sum buffer)
+hipError_t accum_f64_to_f32(const double* sum64, float* sum32, size_t n, hipStream_t stream);
 
 // Render launches.
 hipError_t launch_render(int kernel, int mode, bool stats, const DevScene& S, const DevLaunch& L,
@@ -270,8 +288,6 @@ struct AdaptiveBuffers {
     size_t scan_bytes;
 };
 hipError_t adaptive_scan_bytes(int tiles, size_t* bytes);
-// A mapped launch's k_accum: radiance = the batch's WFState::L, L.n_pixels * nf records in path order.
-hipError_t accum_adaptive(const float4* radiance, const DevLaunch& L, int nf, hipStream_t stream);
 // After a round: e and the tile error of the tiles it rendered, their new state, then adaptive_compact.
 hipError_t adaptive_estimate(const AdaptiveBuffers& A, float threshold, uint32_t min_samples, uint32_t max_samples,
                              float luminance_floor, hipStream_t stream);
@@ -279,12 +295,5 @@ hipError_t adaptive_estimate(const AdaptiveBuffers& A, float threshold, uint32_t
 hipError_t adaptive_compact(const AdaptiveBuffers& A, hipStream_t stream);
 // mean[3 p ..] = sum[3 p ..] / (float)n[p]
 hipError_t adaptive_resolve(const float* sum, const uint32_t* n, float* mean, int pixels, hipStream_t stream);
-
-// Pixel filter (pt_filter.hip).  A filtered launch's k_accum: every frame's image is
-// gathered through the (2 L.ss_R + 1)^2 taps of the frame's cell (L.ss_taps) before it is added.
-// radiance = the batch's WFState::L, L.width * L.height * nf records in path order; L is a whole
-// image (row0 = 0, no pixel map), L.ss_R is 1 or 2.
-constexpr int kFilterMaxR = 2;
-hipError_t accum_filtered(const float4* radiance, const DevLaunch& L, int nf, hipStream_t stream);
 
 }  // namespace pt

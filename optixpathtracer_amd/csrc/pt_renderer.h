@@ -285,7 +285,6 @@ struct pt_renderer {
         // optional per-launch timing of the wavefront's closest-hit trace kernel (k_extend)
         bool kernel_timing = false;
         pt::EventPool tev;
-        std::vector<hipEvent_t> tev_frame;  // 2 * (max_bounces + 1) events handed to one frame
         double trace_ms = 0.0;
         uint64_t trace_launches = 0;
         // the k_trace_pair launches among them (fused modes: every timed trace launch after a batch's
@@ -295,7 +294,6 @@ struct pt_renderer {
         uint64_t pair_launches = 0;
         // the same for the dominant shading kernel of a bounce (pt_stats shade_kernel_*)
         pt::EventPool sev;
-        std::vector<hipEvent_t> sev_frame;
         double shade_ms = 0.0;
         uint64_t shade_launches = 0;
         bool pending = false;
@@ -436,7 +434,7 @@ struct pt_renderer {
         }
     } adaptive;
 
-    // pixel filter (pt_capi_filter.cpp, pt_filter.hip): the setting with radius and param resolved,
+    // pixel filter (pt_capi_filter.cpp, pt_accum.hip): the setting with radius and param resolved,
     // its tap radius R = ceil(radius - 1/2) and the tables the launches point at.  version is part of
     // the render key: no ring frame rendered under another setting is served.
     struct Filter {
@@ -491,8 +489,16 @@ struct PixelMap {
     uint32_t* n;
     double* moments;
 };
-int launch_frames(pt_renderer* r, float* accum, uint32_t first, uint32_t n, double* accum64 = nullptr,
-                  size_t frame_stride = 0, bool speculative = false, const PixelMap* pixels = nullptr);
+// One call of launch_frames: frames first .. first + n - 1 and where they go.
+struct FrameCall {
+    uint32_t first = 0, n = 0;
+    float* accum = nullptr;          // the fp32 sum the frames add into
+    double* accum64 = nullptr;       // pt_set_accum_fp64: the fp64 sum; accum then holds its fp32 rounding
+    size_t frame_stride = 0;         // > 0: frame first + j is written alone to accum + j * frame_stride
+    bool speculative = false;        // a cancellable look-ahead batch (cancel_look_ahead)
+    const PixelMap* pixels = nullptr;  // a mapped call: these pixels of the image only
+};
+int launch_frames(pt_renderer* r, const FrameCall& c);
 int render_frames_multi(pt_renderer* r, uint32_t first, uint32_t n);
 
 // pt_capi_ahead.cpp

@@ -177,7 +177,6 @@ struct EventPool {
         used++;
         return hipSuccess;
     }
-    void give_back(size_t k) { used -= std::min(k, used); }  // the last k pairs went unrecorded
     hipError_t collect(double* ms_sum, size_t* n) {
         *ms_sum = 0.0;
         *n = used;

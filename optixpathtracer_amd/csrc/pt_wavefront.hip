@@ -25,9 +25,9 @@
 //       k_shadow_vis    : any-hit -> vis[shadow ray]; k_nee_compact: visible -> NEE queue
 //       k_shade_nee     : f (may draw), NEE, over the bucketed NEE queue
 //       k_shade_smp     : BSDF sample -> queue b+1, over the bucketed sample queue
-//   k_accum             : accum[pixel] += L[f * P + pixel] for f = 0 .. nf-1 in order (the same
-//                         fp32 order as the sequential reference accumulation); under a pixel filter
-//                         wider than the box, k_accum_filtered (pt_filter.hip) in its place
+//   accum_batch         : the batch's frames added to the destination in frame order, the same fp32
+//                         order as the sequential reference accumulation (pt_accum.hip: k_accum, or
+//                         the filtered or the mapped accumulate in its place)
 //
 // Every kernel reads queue lengths from device memory written by an earlier launch (kernel
 // boundaries order the hand-off), so a whole batch of frames is enqueued without host round trips.
@@ -35,6 +35,7 @@
 #include <unordered_map>
 
 #include "pt_internal.h"
+#include "pt_resource.h"
 #include "pt_shade.h"
 #include "pt_skip.h"
 
@@ -1387,54 +1388,6 @@ __global__ __launch_bounds__(kBlockShB, PT_SMP_WAVES) void k_shade_smp(DevScene 
     }
 }
 
-__global__ __launch_bounds__(kBlockWF) void k_accum(WFState W, DevLaunch L, int nf) {
-    const int P = L.width * L.height;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        const size_t idx = (size_t)p * 3;
-        if (L.frame_stride) {  // render-ahead: each frame its own 1-spp image, a one-frame sum into zeros
-            for (int f = 0; f < nf; ++f) {
-                const float4 l = W.L[(size_t)f * P + p];
-                float* o = L.accum + (size_t)f * L.frame_stride + idx;
-                o[0] = 0.0f + l.x;
-                o[1] = 0.0f + l.y;
-                o[2] = 0.0f + l.z;
-            }
-            continue;
-        }
-        if (L.accum64) {  // pt_set_accum_fp64: the frames' fp32 radiance summed in fp64
-            double sx = L.accum64[idx], sy = L.accum64[idx + 1], sz = L.accum64[idx + 2];
-            for (int f = 0; f < nf; ++f) {
-                const float4 l = W.L[(size_t)f * P + p];
-                sx += (double)l.x;
-                sy += (double)l.y;
-                sz += (double)l.z;
-            }
-            L.accum64[idx] = sx;
-            L.accum64[idx + 1] = sy;
-            L.accum64[idx + 2] = sz;
-            L.accum[idx] = (float)sx;
-            L.accum[idx + 1] = (float)sy;
-            L.accum[idx + 2] = (float)sz;
-            continue;
-        }
-        float sx = L.accum[idx], sy = L.accum[idx + 1], sz = L.accum[idx + 2];
-        for (int f = 0; f < nf; ++f) {  // frames in order: the sequential accumulation
-            const float4 l = W.L[(size_t)f * P + p];
-            sx += l.x;
-            sy += l.y;
-            sz += l.z;
-        }
-        L.accum[idx] = sx;
-        L.accum[idx + 1] = sy;
-        L.accum[idx + 2] = sz;
-    }
-}
-
-__global__ __launch_bounds__(kBlockWF) void k_f64_to_f32(const double* __restrict__ a, float* __restrict__ b, size_t n) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        b[i] = (float)a[i];
-}
-
 inline bool fused_mode(int mode) { return mode == kModeLambert || mode == kModeConductor || mode == kModeDielectric; }
 
 // Grid covering `items` slots, one per thread.
@@ -1536,12 +1489,6 @@ hipError_t launch_shade_mode(int mode, bool fused, const DevScene& S, const DevL
 
 }  // namespace
 
-hipError_t accum_f64_to_f32(const double* sum64, float* sum32, size_t n, hipStream_t stream) {
-    const unsigned blocks = (unsigned)std::min<size_t>((n + kBlockWF - 1) / kBlockWF, 8192);
-    hipLaunchKernelGGL(k_f64_to_f32, dim3(std::max(1u, blocks)), dim3(kBlockWF), 0, stream, sum64, sum32, n);
-    return hipGetLastError();
-}
-
 size_t wavefront_bytes(int paths, int max_bounces) {
     size_t P = (size_t)paths;
     return P * sizeof(float4) * (4 /*rays x2 queues*/ + 1 /*hit*/ + 3 /*beta x2, L*/ + 3 /*shadow*/) +
@@ -1590,11 +1537,11 @@ void wavefront_free(WFState& W) {
     W = WFState{};
 }
 
-hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const DevLaunch& L, const WFState& W,
-                                  uint32_t frame, int nf, bool primary_dedup, int cus, hipStream_t stream,
-                                  const hipEvent_t* trace_events, int* n_timed, hipEvent_t accum_wait,
-                                  hipEvent_t accum_done, const hipEvent_t* shade_events, int* n_shade_timed,
-                                  bool wide_trace) {
+hipError_t launch_wavefront_batch(const DevScene& S, const DevLaunch& L, const WFState& W, const WFBatch& B) {
+    const int mode = B.mode, cus = B.cus;
+    const bool stats = B.stats, primary_dedup = B.primary_dedup, wide_trace = B.wide_trace;
+    const hipStream_t stream = B.stream;
+    const int nf = (int)L.n_frames;  // the batch's frames: L.frame_base .. L.frame_base + nf - 1
     const int P = L.n_pixels * nf;  // paths in flight
     const int maxb = L.max_bounces;
     hipError_t e = hipSuccess;
@@ -1607,30 +1554,21 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
     // fused modes with the primary dedup: frame 0's camera rays only (k_camera `lean`, shade0)
     const bool lean = fused_mode(mode) && primary_dedup && nf > 1 && maxb > 0;
     hipLaunchKernelGGL(k_camera, item_grid(lean ? L.n_pixels : P, kBlockWF), dim3(kBlockWF), 0, stream, W, L,
-                       frame, nf, lean ? 1 : 0);
+                       L.frame_base, nf, lean ? 1 : 0);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const bool fused = fused_mode(mode);
     const bool tex = S.texinfo != nullptr;  // textured scene: kernels with texture sampling
-    int timed = 0;                          // trace launches bracketed by trace_events
-    int stimed = 0;                         // shading launches bracketed by shade_events
-    // the timed shading kernel of a bounce: k_shade_fused / k_shade0_pixel (fused modes), k_shade_nee
-    // (Default / Layered: the stochastic layered eval, 53-60 % of their frame)
-    auto shade_timed = [&](auto launch) -> hipError_t {
+    // pt_set_kernel_timing: the launch between an event pair of `pool` (null: not timed).  Timed are
+    // the k_extend and k_trace_pair launches and the dominant shading kernel of a bounce: k_shade_fused
+    // / k_shade0_pixel (fused modes), k_shade_nee (Default / Layered: the stochastic layered eval,
+    // 53-60 % of their frame)
+    auto timed = [&](EventPool* pool, auto launch) -> hipError_t {
+        if (!pool) return launch();
+        hipEvent_t a = nullptr, b = nullptr;
         hipError_t r;
-        if (shade_events && (r = hipEventRecord(shade_events[2 * stimed], stream)) != hipSuccess) return r;
+        if ((r = pool->next(&a, &b)) != hipSuccess || (r = hipEventRecord(a, stream)) != hipSuccess) return r;
         if ((r = launch()) != hipSuccess) return r;
-        if (shade_events && (r = hipEventRecord(shade_events[2 * stimed + 1], stream)) != hipSuccess) return r;
-        ++stimed;
-        return hipSuccess;
-    };
-    // as shade_timed, for the trace launches of the fused modes' bounces and k_extend
-    auto trace_timed = [&](auto launch) -> hipError_t {
-        hipError_t r;
-        if (trace_events && (r = hipEventRecord(trace_events[2 * timed], stream)) != hipSuccess) return r;
-        if ((r = launch()) != hipSuccess) return r;
-        if (trace_events && (r = hipEventRecord(trace_events[2 * timed + 1], stream)) != hipSuccess) return r;
-        ++timed;
-        return hipSuccess;
+        return hipEventRecord(b, stream);
     };
     // a trace kernel on exactly the workgroups that are resident at once; wide_trace: the trace
     // kernels of a one-stream call take the wide workgroups (kBlockTraceWide)
@@ -1639,14 +1577,14 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
         return hipGetLastError();
     };
     auto extend = [&](int b, int dup, int copies) -> hipError_t {
-        return trace_timed([&] {
+        return timed(B.timers.extend, [&] {
             return trace_variant(tex, wide_trace, stats, [&](auto tx, auto st, auto blk) {
                 return trace_launch(k_extend<st(), tx(), blk()>, blk(), S, W, b, dup, copies, L.counters);
             });
         });
     };
     auto pair = [&](int b) -> hipError_t {
-        return trace_timed([&] {
+        return timed(B.timers.pair, [&] {
             return trace_variant(tex, wide_trace, stats, [&](auto tx, auto st, auto blk) {
                 return with_flag(L.skip_tab != nullptr, [&](auto sk) {
                     return trace_launch(k_trace_pair<st(), tx(), blk(), sk()>, blk(), S, W, b, L.counters);
@@ -1686,9 +1624,9 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
         if ((e = shadow0()) != hipSuccess) return e;
         for (int b = 0; b < maxb; ++b) {
             if (b == 0 && pixel0) {
-                if ((e = shade_timed([&] { return launch_shade0_pixel(mode, S, L, W, nf, stream); })) != hipSuccess)
+                if ((e = timed(B.timers.shade, [&] { return launch_shade0_pixel(mode, S, L, W, nf, stream); })) != hipSuccess)
                     return e;
-            } else if ((e = shade_timed([&] {
+            } else if ((e = timed(B.timers.shade, [&] {
                             return launch_shade_mode(mode, true, S, L, W, b, P, stream, 0, b == 0 ? vis0 : 0,
                                                      b == 0 && lean);
                         })) != hipSuccess) {
@@ -1706,24 +1644,16 @@ hipError_t launch_wavefront_frame(int mode, bool stats, const DevScene& S, const
             // or k_shadow_vis + k_nee_compact) get the NEE eval, the continuing ones the sample
             if ((e = launch_shade_mode(mode, false, S, L, W, b, P, stream, 0, v0)) != hipSuccess) return e;
             if (!v0 && (e = shadow_vis(b, 0)) != hipSuccess) return e;
-            if ((e = shade_timed([&] { return launch_shade_mode(mode, false, S, L, W, b, P, stream, 1, v0); })) !=
+            if ((e = timed(B.timers.shade, [&] { return launch_shade_mode(mode, false, S, L, W, b, P, stream, 1, v0); })) !=
                 hipSuccess)
                 return e;
             if (b + 1 < maxb && (e = launch_shade_mode(mode, false, S, L, W, b, P, stream, 2, v0)) != hipSuccess)
                 return e;
         }
     }
-    if (accum_wait && (e = hipStreamWaitEvent(stream, accum_wait, 0)) != hipSuccess) return e;
-    if (L.pixel_map) {
-        if ((e = accum_adaptive(W.L, L, nf, stream)) != hipSuccess) return e;
-    } else if (L.ss_taps) {  // a pixel filter wider than the box (pt_filter.hip)
-        if ((e = accum_filtered(W.L, L, nf, stream)) != hipSuccess) return e;
-    } else {
-        hipLaunchKernelGGL(k_accum, item_grid(L.width * L.height, kBlockWF), dim3(kBlockWF), 0, stream, W, L, nf);
-    }
-    if (accum_done && (e = hipEventRecord(accum_done, stream)) != hipSuccess) return e;
-    if (n_timed) *n_timed = timed;  // fused modes: max_bounces + 1; Default / Layered: max_bounces
-    if (n_shade_timed) *n_shade_timed = stimed;  // max_bounces
+    if (B.accum_wait && (e = hipStreamWaitEvent(stream, B.accum_wait, 0)) != hipSuccess) return e;
+    if ((e = accum_batch(W.L, L, nf, stream)) != hipSuccess) return e;
+    if (B.accum_done && (e = hipEventRecord(B.accum_done, stream)) != hipSuccess) return e;
     return hipGetLastError();
 }
 

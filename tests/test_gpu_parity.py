@@ -424,17 +424,19 @@ def test_bucketed_shading_queues(variant, mode, n_lights):
         np.testing.assert_array_equal(mega, o)
 
 
-@pytest.mark.parametrize("mode", [1, 0])
-def test_trace_kernel_timing_counts_every_launch(mode):
+@pytest.mark.parametrize("mode,depth", [(1, 3), (0, 3), (1, 0)], ids=["1", "0", "1-no-bounces"])
+def test_trace_kernel_timing_counts_every_launch(mode, depth):
     """pt_set_kernel_timing brackets every trace launch with an event pair (bench.py's
     roofline): fused modes trace max_bounces + 1 times per batch (k_extend, then one
-    k_trace_pair per bounce), Default / Layered max_bounces times (k_extend per bounce)."""
+    k_trace_pair per bounce), Default / Layered max_bounces times (k_extend per bounce), and either
+    times one shading launch per bounce.  At 0 bounces a batch launches none of them, no pair is
+    counted, and the frames are black."""
     from optixpathtracer_amd import scenes
     from optixpathtracer_amd.capi import PTError
     from optixpathtracer_amd.renderer import setup_renderer
 
     sc = scenes.tiny_scene("diffuse")
-    depth, spp, fpl = 3, 10, 4
+    spp, fpl = 10, 4
     r = setup_renderer(sc, 32, 24, depth, kernel=1)
     r.set_material_mode(mode)
     r.set_frames_per_launch(fpl)
@@ -444,9 +446,15 @@ def test_trace_kernel_timing_counts_every_launch(mode):
     r.synchronize()
     st = r.stats()
     batches = -(-spp // fpl)
-    per_batch = depth + 1 if mode == 1 else depth
+    fused = mode == 1
+    per_batch = 0 if depth == 0 else depth + 1 if fused else depth
     assert st["trace_kernel_launches"] == batches * per_batch
-    assert st["trace_kernel_ms"] > 0.0
+    assert st["shade_kernel_launches"] == batches * depth
+    assert st["pair_kernel_launches"] == (batches * depth if fused else 0)
+    if depth > 0:
+        assert st["trace_kernel_ms"] > 0.0
+    else:
+        assert not r.accum().any()
     with pytest.raises(PTError):
         r.SetMaxBounces(-1)
     r.close()
