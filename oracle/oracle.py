@@ -2,8 +2,8 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this
 module; the product (optixpathtracer_amd/) never does.  See pt_oracle.h for the parity
-status ("parity unpinned" against the OptiX original, pinned by the reference's own unit
-test known answers only).
+status: BSDFs, RNG and camera are pinned bit for bit against the reference's host-compiled
+headers (tests/test_oracle_vs_reference.py); the path loop is still a reading by hand.
 """
 from __future__ import annotations
 
@@ -96,6 +96,13 @@ def load() -> C.CDLL:
     lib.orc_bsdf_pdf.argtypes = [C.c_int32, C.c_float, _FP, _FP]
     lib.orc_bsdf_sample_n.argtypes = [C.c_int32, _UP, _FP, C.c_float, _FP, C.c_int32, _FP, C.POINTER(C.c_int32)]
     lib.orc_bsdf_pdf_n.argtypes = [C.c_int32, C.c_float, _FP, _FP, C.c_int32, _FP]
+    _IP = C.POINTER(C.c_int32)
+    lib.orc_bsdf_sample_cases.restype = None
+    lib.orc_bsdf_sample_cases.argtypes = [C.c_int32, C.c_int32, _UP, _FP, _FP, _FP, _FP, _IP]
+    lib.orc_bsdf_eval_cases.restype = None
+    lib.orc_bsdf_eval_cases.argtypes = [C.c_int32, C.c_int32, _UP, _FP, _FP, _FP, _FP, _FP]
+    lib.orc_bsdf_pdf_cases.restype = None
+    lib.orc_bsdf_pdf_cases.argtypes = [C.c_int32, C.c_int32, _FP, _FP, _FP, _FP]
     lib.orc_cos_theta.restype = C.c_float
     lib.orc_cos_theta.argtypes = [_FP]
     lib.orc_furnace.argtypes = [C.c_int32, _UP, _FP, C.c_float, _FP, C.c_int32, _FP]

@@ -11,7 +11,8 @@
  * Choices the reference leaves to closed code (OptiX 7.3 traversal) are documented where
  * made: Moller-Trumbore triangle test with OptiX barycentric convention (u weights v1,
  * v weights v2), closed-interval [tmin,tmax], closest hit ordered by (t, global primitive
- * index) so the result is independent of the acceleration structure.  "parity unpinned".
+ * index) so the result is independent of the acceleration structure.  That part is "parity
+ * unpinned"; the BSDFs, the RNG and the camera are pinned bit for bit (pt_oracle.h).
  */
 #include "pt_oracle.h"
 
@@ -815,6 +816,25 @@ void orc_bsdf_sample_n(int32_t model, uint32_t* seed, const float albedo[3], flo
 }
 void orc_bsdf_pdf_n(int32_t model, float roughness, const float wo[3], const float* wi3, int32_t n, float* out) {
     for (int32_t k = 0; k < n; ++k) out[k] = orc_bsdf_pdf(model, roughness, wo, wi3 + 3 * (size_t)k);
+}
+/* Batched forms for the reference comparison (tests/test_oracle_vs_reference.py): n independent
+ * cases, each with its own seed (advanced in place), albedo, roughness and directions. */
+void orc_bsdf_sample_cases(int32_t model, int32_t n, uint32_t* seeds, const float* albedo3, const float* roughness,
+                           const float* wo3, float* out8, int32_t* ok) {
+    for (int32_t k = 0; k < n; ++k)
+        ok[k] = orc_bsdf_sample(model, seeds + k, albedo3 + 3 * (size_t)k, roughness[k], wo3 + 3 * (size_t)k,
+                                out8 + 8 * (size_t)k);
+}
+void orc_bsdf_eval_cases(int32_t model, int32_t n, uint32_t* seeds, const float* albedo3, const float* roughness,
+                         const float* wo3, const float* wi3, float* out3) {
+    for (int32_t k = 0; k < n; ++k)
+        orc_bsdf_eval(model, seeds + k, albedo3 + 3 * (size_t)k, roughness[k], wo3 + 3 * (size_t)k,
+                      wi3 + 3 * (size_t)k, out3 + 3 * (size_t)k);
+}
+void orc_bsdf_pdf_cases(int32_t model, int32_t n, const float* roughness, const float* wo3, const float* wi3,
+                        float* out) {
+    for (int32_t k = 0; k < n; ++k)
+        out[k] = orc_bsdf_pdf(model, roughness[k], wo3 + 3 * (size_t)k, wi3 + 3 * (size_t)k);
 }
 
 /* ------------------------------------------------------------------------------------ */

@@ -6,11 +6,21 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it, and only as the
  * checker / the timed CPU baseline.  The product (optixpathtracer_amd/) never links it.
  *
- * Parity status: the reference cannot be compiled or run here (no nvcc/OptiX/NVIDIA GPU;
- * host-compiling its headers was denied by the environment).  This
- * restatement is therefore pinned only by the reference's own known answers
- * (UnitTests/SpherGeom_Test.cpp: CosTheta KAT + furnace bounds) and by the standard
- * TEA/LCG constants; everything else is "parity unpinned" against the OptiX original.
+ * Parity status (tests/test_oracle_vs_reference.py):
+ *  - PINNED bit for bit against the reference's own headers, host-compiled by oracle/Makefile
+ *    into oracle/_ref/ behind oracle/ptref_capi.cpp: the four BSDFs (Sample_f, f, PDF: return
+ *    value, colour, pdf, direction, flags, the seed afterwards), tea<16> / rnd, and the camera
+ *    (Camera.cpp + GlmHelperMethods.cpp composed as OptixRenderer::SetCamera does).  Where the
+ *    reference tree is absent the same bits are held as data (tests/golden/reference_bsdf.npz).
+ *    The transcendentals are the exception by design: the reference calls libdevice's
+ *    sinf/cosf/expf, this file and the kernels fixed polynomials (orc_math_eval), and the
+ *    comparison puts those polynomials behind the reference's calls.
+ *  - STILL READ BY HAND: devicePrograms.cu itself, which needs OptiX: SamplePath, NEE, the
+ *    closest-hit dispatch and the texture fetches, and the traversal inside the OptiX runtime.
+ *    Those are pinned by the reference's unit-test known answers (UnitTests/SpherGeom_Test.cpp)
+ *    and the second readings in tests/ only.
+ *  - PINNED BY PTX ONLY: the float -> unsigned cast of a negative value in the Layered private
+ *    seed (GlossyDiffuse.h:215-217, :417; orc_f2u_sat), which is undefined on the host.
  */
 #ifndef PT_ORACLE_H
 #define PT_ORACLE_H
@@ -84,6 +94,14 @@ float orc_bsdf_pdf(int32_t model, float roughness, const float wo[3], const floa
 void orc_bsdf_sample_n(int32_t model, uint32_t* seed, const float albedo[3], float roughness, const float wo[3],
                        int32_t n, float* out8, int32_t* ok);
 void orc_bsdf_pdf_n(int32_t model, float roughness, const float wo[3], const float* wi3, int32_t n, float* out);
+/* n independent cases (own seed, albedo, roughness, directions each); ptref_capi.cpp exports
+ * the reference's side of these as ref_bsdf_{sample,eval,pdf}_n */
+void orc_bsdf_sample_cases(int32_t model, int32_t n, uint32_t* seeds, const float* albedo3, const float* roughness,
+                           const float* wo3, float* out8, int32_t* ok);
+void orc_bsdf_eval_cases(int32_t model, int32_t n, uint32_t* seeds, const float* albedo3, const float* roughness,
+                         const float* wo3, const float* wi3, float* out3);
+void orc_bsdf_pdf_cases(int32_t model, int32_t n, const float* roughness, const float* wo3, const float* wi3,
+                        float* out);
 /* reference unit-test known answers (UnitTests/SpherGeom_Test.cpp) */
 float orc_cos_theta(const float w[3]);
 void orc_furnace(int32_t model, uint32_t* seed, const float albedo[3], float roughness, const float wo[3],

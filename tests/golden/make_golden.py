@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures in tests/golden/ from the CPU oracle (oracle/liboracle.so).
 
-The reference (Damo12320/OptixPathtracer) cannot be built or run here (OptiX/CUDA only;
-host compilation of its headers was denied), so these vectors are the
-build's own CPU restatement frozen as data: they pin the oracle against regressions and
+The reference (Damo12320/OptixPathtracer) renders with OptiX/CUDA only, so these vectors are
+the build's own CPU restatement frozen as data: they pin the oracle against regressions and
 give the GPU tests a committed target.  The restatement itself is pinned by the
 reference's own known answers (tests/test_oracle.py: TEA/LCG constants, CosTheta KAT,
-furnace bounds of UnitTests/SpherGeom_Test.cpp).
+furnace bounds of UnitTests/SpherGeom_Test.cpp) and, for the BSDFs, RNG and camera, by the
+reference's host-compiled headers (tests/test_oracle_vs_reference.py; that comparison has its
+own fixture, reference_bsdf.npz, which holds the REFERENCE's results, not the oracle's).
 
     python tests/golden/make_golden.py      # rewrites tests/golden/golden.npz
 """
