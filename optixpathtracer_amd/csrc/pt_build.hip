@@ -13,8 +13,13 @@
 //                   BVH4 level at a time (k_collapse_count -> scan -> k_collapse_emit), numbering
 //                   the nodes breadth-first by a prefix sum: the node array is the same on every
 //                   build (no atomic slot order), and the top levels are a contiguous prefix.
+// Steps 1-5 are the Karras LBVH front end.  bvh_build runs one of four front ends, each of which
+// leaves a binary tree (BinaryTree) and the triangle records in leaf order, and then the one back
+// end, step 6.  The other front ends: PLOC below, the host binned-SAH tree (pt_sah.cpp) and the same
+// tree built on the GPU (pt_sah_gpu.hip), which is the default.  Every stage's scratch is a set of
+// DevBufs of its own; bvh_build holds them so that they are freed after the timed window.
 // PLOC builder (Meister & Bittner 2018, "Parallel Locally-Ordered Clustering for Bounding
-// Volume Hierarchy Construction"), the default: starting from the Morton-sorted leaves, each
+// Volume Hierarchy Construction"): starting from the Morton-sorted leaves, each
 // iteration finds every cluster's nearest neighbour (smallest merged surface area) within
 // +-kPlocRadius positions, merges mutual pairs and compacts (hipCUB scan).  A top-down pass
 // then numbers the leaves in depth-first order, so every subtree is again a contiguous
@@ -29,6 +34,7 @@
 #include <vector>
 
 #include "pt_internal.h"
+#include "pt_resource.h"
 
 namespace pt {
 
@@ -525,313 +531,377 @@ __global__ void k_ploc_total(const unsigned long long* scan, const unsigned long
     out[1] = (int)(t >> 32);          // nodes created
 }
 
-// Host sequencing of the PLOC iterations and the DFS numbering; fills B, the triangle
-// records in DFS leaf order and the binary root code.  One host sync per iteration / level
-// (the loop bounds come from device counts); allocations are appended to `owned`.
-hipError_t ploc_build(const BuildInput& in, const uint32_t* morton_order, BuildOutput& out, hipStream_t stream,
-                      BinTree& B, int& root, std::vector<void*>& owned) {
-    const int n = in.n;
-    hipError_t err = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (err == hipSuccess) err = hipMalloc(p, bytes > 0 ? bytes : 16);
-        if (err == hipSuccess) owned.push_back(*p);
-    };
-    const int nb = n > 1 ? n - 1 : 1;
-    float4 *box[2] = {nullptr, nullptr}, *bbox = nullptr, *leafbox = nullptr, *pleaf = nullptr;
-    int *code[2] = {nullptr, nullptr}, *ccnt[2] = {nullptr, nullptr}, *nn = nullptr, *bcount = nullptr,
-        *tot = nullptr;
-    unsigned long long *flags = nullptr, *scan = nullptr;
-    int2 *bchild = nullptr, *brange = nullptr, *work[2] = {nullptr, nullptr};
-    uint32_t* dfs = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    for (int k = 0; k < 2; ++k) {
-        alloc((void**)&box[k], sizeof(float4) * 2 * (size_t)n);
-        alloc((void**)&code[k], sizeof(int) * (size_t)n);
-        alloc((void**)&ccnt[k], sizeof(int) * (size_t)n);
-        alloc((void**)&work[k], sizeof(int2) * (size_t)n);
+// hipCUB temp storage: at least 16 bytes, since a computed size can be 0.
+hipError_t alloc_temp(DevBuf<unsigned char>& temp, size_t bytes) { return temp.alloc(bytes > 0 ? bytes : 16); }
+
+// The device arrays a BinTree points into and the binary root code (node 0, or ~0 when the one
+// triangle is the root).  A front end fills everything but pbox, which the back end adds.
+struct BinaryTree {
+    DevBuf<int2> child, range;
+    DevBuf<float4> box, leafbox, pleaf, pbox;
+    int root = 0;
+    BinTree view() const { return BinTree{child, range, box, leafbox, pleaf, pbox}; }
+    // n - 1 internal nodes (one slot at n = 1) and n leaves; `leafboxes`: float4 pairs in leafbox
+    hipError_t alloc(int n, size_t leafboxes) {
+        const size_t nbin = n > 1 ? n - 1 : 1;
+        return first_error({child.alloc(nbin), range.alloc(nbin), box.alloc(2 * nbin), leafbox.alloc(2 * leafboxes),
+                            pleaf.alloc(2 * (size_t)n)});
     }
-    alloc((void**)&nn, sizeof(int) * (size_t)n);
-    alloc((void**)&flags, sizeof(unsigned long long) * (size_t)n);
-    alloc((void**)&scan, sizeof(unsigned long long) * (size_t)n);
-    alloc((void**)&bchild, sizeof(int2) * (size_t)nb);
-    alloc((void**)&brange, sizeof(int2) * (size_t)nb);
-    alloc((void**)&bbox, sizeof(float4) * 2 * (size_t)nb);
-    alloc((void**)&bcount, sizeof(int) * (size_t)nb);
-    alloc((void**)&leafbox, sizeof(float4) * 2 * (size_t)n);
-    alloc((void**)&pleaf, sizeof(float4) * 2 * (size_t)n);
-    alloc((void**)&dfs, sizeof(uint32_t) * (size_t)n);
-    alloc((void**)&tot, sizeof(int) * 2);
-    if (err != hipSuccess) return err;
-    if ((err = hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, flags, scan, n, stream)) != hipSuccess)
+};
+
+// Every front end's last step on the triangles: the records in leaf order into `out`, the leaves'
+// plain and padded boxes into the tree.
+hipError_t gather_leaves(const BuildInput& in, const uint32_t* order, BuildOutput& out, BinaryTree& T,
+                         hipStream_t stream) {
+    hipLaunchKernelGGL(k_gather, dim3(grid_for(in.n, 256)), dim3(256), 0, stream, in.tri_orig, in.nrm_orig, in.uv_orig,
+                       order, in.n, out.isect, out.shade, out.tuv, T.leafbox.get(), T.pleaf.get());
+    return hipGetLastError();
+}
+
+// Morton keys of the triangles and the triangles sorted by them: what the LBVH and PLOC front
+// ends start from.
+struct MortonOrder {
+    DevBuf<uint32_t> keys, vals, keys2, vals2;  // keys2 / vals2: the sorted keys and their triangles
+    DevBuf<unsigned char> temp;
+    size_t temp_bytes = 0;
+    hipError_t alloc(int n, hipStream_t stream) {
+        hipError_t err = first_error({keys.alloc(n), vals.alloc(n), keys2.alloc(n), vals2.alloc(n)});
+        if (err != hipSuccess) return err;
+        err = hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys.get(), keys2.get(), vals.get(), vals2.get(),
+                                                 n, 0, 30, stream);
+        return err != hipSuccess ? err : alloc_temp(temp, temp_bytes);
+    }
+    hipError_t sort(const BuildInput& in, hipStream_t stream) {
+        const int n = in.n;
+        float3 cmin = make_float3(in.cmin[0], in.cmin[1], in.cmin[2]);
+        float ex = in.cmax[0] - in.cmin[0], ey = in.cmax[1] - in.cmin[1], ez = in.cmax[2] - in.cmin[2];
+        float3 cinv = make_float3(ex > 0.0f ? 1.0f / ex : 0.0f, ey > 0.0f ? 1.0f / ey : 0.0f,
+                                  ez > 0.0f ? 1.0f / ez : 0.0f);
+        hipLaunchKernelGGL(k_morton, dim3(grid_for(n, 256)), dim3(256), 0, stream, in.tri_orig, n, cmin, cinv,
+                           keys.get(), vals.get());
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+        return hipcub::DeviceRadixSort::SortPairs(temp.get(), temp_bytes, keys.get(), keys2.get(), vals.get(),
+                                                  vals2.get(), n, 0, 30, stream);
+    }
+};
+
+// The front ends.  Each builds the binary tree of `in` into T and writes the triangle records in
+// leaf order into `out`.  What it allocates before it records `start` is outside the build's
+// timed window.  Its scratch is the caller's, empty on entry: bvh_build releases it after the stop
+// event, because a hipFree waits for the device and takes its own time, both of which the window
+// would count (at 10^6 triangles PLOC measured 15 ms instead of 10 with the frees inside).
+
+// Karras 2012: the tree over the Morton-sorted triangles, boxes from a sparse table over the leaves
+// (T.leafbox holds the whole table; level 0 is the leaf boxes).
+hipError_t build_lbvh(const BuildInput& in, BuildOutput& out, hipStream_t stream, hipEvent_t start,
+                      MortonOrder& morton, BinaryTree& T) {
+    const int n = in.n;
+    int levels = 1;
+    while ((1 << levels) <= n) ++levels;  // levels 0..levels-1 with 2^l <= n
+    hipError_t err;
+    if ((err = first_error({morton.alloc(n, stream), T.alloc(n, (size_t)n * (size_t)levels)})) != hipSuccess)
         return err;
-    alloc(&temp, temp_bytes);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_leafbox, dim3(grid_for(n, 256)), dim3(256), 0, stream, in.tri_orig, morton_order, n, box[0],
-                       code[0], ccnt[0]);
+    if ((err = hipEventRecord(start, stream)) != hipSuccess) return err;
+    if ((err = morton.sort(in, stream)) != hipSuccess) return err;
+    if ((err = gather_leaves(in, morton.vals2, out, T, stream)) != hipSuccess) return err;
+    SparseTable table{};
+    float4* const st = T.leafbox;
+    table.n = n;
+    table.level[0] = st;
+    for (int l = 1; l < levels; ++l) {
+        float4* prev = st + 2 * (size_t)n * (size_t)(l - 1);
+        float4* cur = st + 2 * (size_t)n * (size_t)l;
+        int count = n - (1 << l) + 1;
+        hipLaunchKernelGGL(k_sparse, dim3(grid_for(count, 256)), dim3(256), 0, stream, prev, cur, count, 1 << (l - 1));
+        if ((err = hipGetLastError()) != hipSuccess) return err;
+        table.level[l] = cur;
+    }
+    if (n > 1) {
+        hipLaunchKernelGGL(k_karras, dim3(grid_for(n - 1, 256)), dim3(256), 0, stream, morton.keys2.get(), n, table,
+                           T.child.get(), T.range.get(), T.box.get());
+        if ((err = hipGetLastError()) != hipSuccess) return err;
+    }
+    T.root = n > 1 ? 0 : ~0;
+    return hipSuccess;
+}
+
+// PLOC's working set: the cluster arrays (two of each, read and written in turn), the iteration's
+// neighbour / flag / scan arrays, the nodes' leaf counts, the DFS work lists and the DFS order.
+struct PlocScratch {
+    DevBuf<float4> box[2];
+    DevBuf<int> code[2], ccnt[2], nn, bcount, tot;
+    DevBuf<int2> work[2];
+    DevBuf<unsigned long long> flags, scan;
+    DevBuf<uint32_t> dfs;
+    DevBuf<unsigned char> temp;
+    size_t temp_bytes = 0;
+    hipError_t alloc(int n, hipStream_t stream) {
+        const size_t nb = n > 1 ? n - 1 : 1;
+        hipError_t err = hipSuccess;
+        for (int k = 0; k < 2 && err == hipSuccess; ++k)
+            err = first_error({box[k].alloc(2 * (size_t)n), code[k].alloc(n), ccnt[k].alloc(n), work[k].alloc(n)});
+        if (err == hipSuccess)
+            err = first_error(
+                {nn.alloc(n), flags.alloc(n), scan.alloc(n), bcount.alloc(nb), dfs.alloc(n), tot.alloc(2)});
+        if (err == hipSuccess)
+            err = hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, flags.get(), scan.get(), n, stream);
+        return err != hipSuccess ? err : alloc_temp(temp, temp_bytes);
+    }
+};
+
+// The PLOC iterations: nearest neighbours, mutual pairs merged into nodes, clusters compacted, until
+// one cluster is left; *root = its code.  One host sync per iteration (the counts come from the device).
+hipError_t ploc_cluster(const BuildInput& in, const uint32_t* morton_order, PlocScratch& S, BinaryTree& T,
+                        hipStream_t stream, int* root) {
+    const int n = in.n;
+    hipError_t err;
+    hipLaunchKernelGGL(k_leafbox, dim3(grid_for(n, 256)), dim3(256), 0, stream, in.tri_orig, morton_order, n,
+                       S.box[0].get(), S.code[0].get(), S.ccnt[0].get());
     if ((err = hipGetLastError()) != hipSuccess) return err;
     int cur = 0, m = n, node_base = 0;
     while (m > 1) {
-        hipLaunchKernelGGL(k_ploc_nn, dim3(grid_for(m, 256)), dim3(256), 0, stream, box[cur], m, nn);
-        hipLaunchKernelGGL(k_ploc_flags, dim3(grid_for(m, 256)), dim3(256), 0, stream, nn, m, flags);
+        hipLaunchKernelGGL(k_ploc_nn, dim3(grid_for(m, 256)), dim3(256), 0, stream, S.box[cur].get(), m, S.nn.get());
+        hipLaunchKernelGGL(k_ploc_flags, dim3(grid_for(m, 256)), dim3(256), 0, stream, S.nn.get(), m, S.flags.get());
         if ((err = hipGetLastError()) != hipSuccess) return err;
-        if ((err = hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, flags, scan, m, stream)) != hipSuccess)
+        if ((err = hipcub::DeviceScan::ExclusiveSum(S.temp.get(), S.temp_bytes, S.flags.get(), S.scan.get(), m,
+                                                    stream)) != hipSuccess)
             return err;
-        hipLaunchKernelGGL(k_ploc_compact, dim3(grid_for(m, 256)), dim3(256), 0, stream, box[cur], code[cur],
-                           ccnt[cur], nn, scan, flags, m, node_base, box[cur ^ 1], code[cur ^ 1], ccnt[cur ^ 1],
-                           bchild, bbox, bcount);
-        hipLaunchKernelGGL(k_ploc_total, dim3(1), dim3(1), 0, stream, scan, flags, m, tot);
+        hipLaunchKernelGGL(k_ploc_compact, dim3(grid_for(m, 256)), dim3(256), 0, stream, S.box[cur].get(),
+                           S.code[cur].get(), S.ccnt[cur].get(), S.nn.get(), S.scan.get(), S.flags.get(), m, node_base,
+                           S.box[cur ^ 1].get(), S.code[cur ^ 1].get(), S.ccnt[cur ^ 1].get(), T.child.get(),
+                           T.box.get(), S.bcount.get());
+        hipLaunchKernelGGL(k_ploc_total, dim3(1), dim3(1), 0, stream, S.scan.get(), S.flags.get(), m, S.tot.get());
         if ((err = hipGetLastError()) != hipSuccess) return err;
         int h[2] = {0, 0};
-        if ((err = hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, stream)) != hipSuccess) return err;
+        if ((err = hipMemcpyAsync(h, S.tot, sizeof h, hipMemcpyDeviceToHost, stream)) != hipSuccess) return err;
         if ((err = hipStreamSynchronize(stream)) != hipSuccess) return err;
         if (h[1] <= 0) return hipErrorUnknown;  // cannot happen: the best pair is always mutual
         m = h[0];
         node_base += h[1];
         cur ^= 1;
     }
+    if ((err = hipMemcpyAsync(root, S.code[cur], sizeof(int), hipMemcpyDeviceToHost, stream)) != hipSuccess) return err;
+    return hipStreamSynchronize(stream);
+}
+
+// Depth-first leaf numbering from the root node `rc`, one launch and one host sync per tree level:
+// every subtree becomes a contiguous leaf range, S.dfs the triangle of every leaf.
+hipError_t ploc_number(int rc, const uint32_t* morton_order, PlocScratch& S, BinaryTree& T, hipStream_t stream) {
+    hipError_t err;
+    int2 w0 = make_int2(rc, 0);
+    int nwork = 1, c = 0;
+    int* nnext = S.tot;
+    if ((err = hipMemcpyAsync(S.work[0], &w0, sizeof(int2), hipMemcpyHostToDevice, stream)) != hipSuccess) return err;
+    while (nwork > 0) {
+        if ((err = hipMemsetAsync(nnext, 0, sizeof(int), stream)) != hipSuccess) return err;
+        hipLaunchKernelGGL(k_ploc_dfs, dim3(grid_for(nwork, 128)), dim3(128), 0, stream, S.work[c].get(), nwork,
+                           T.child.get(), S.bcount.get(), T.range.get(), morton_order, S.dfs.get(), S.work[c ^ 1].get(),
+                           nnext);
+        if ((err = hipGetLastError()) != hipSuccess) return err;
+        if ((err = hipMemcpyAsync(&nwork, nnext, sizeof(int), hipMemcpyDeviceToHost, stream)) != hipSuccess) return err;
+        if ((err = hipStreamSynchronize(stream)) != hipSuccess) return err;
+        c ^= 1;
+    }
+    return hipSuccess;
+}
+
+// PLOC (Meister & Bittner 2018) over the Morton-sorted triangles.  Also the SAH builders' tree of a
+// single triangle.
+hipError_t build_ploc(const BuildInput& in, BuildOutput& out, hipStream_t stream, hipEvent_t start,
+                      MortonOrder& morton, PlocScratch& S, BinaryTree& T) {
+    const int n = in.n;
+    hipError_t err;
+    if ((err = morton.alloc(n, stream)) != hipSuccess) return err;
+    if ((err = hipEventRecord(start, stream)) != hipSuccess) return err;
+    if ((err = morton.sort(in, stream)) != hipSuccess) return err;
+    if ((err = first_error({S.alloc(n, stream), T.alloc(n, n)})) != hipSuccess) return err;
     int rc = ~0;
-    if ((err = hipMemcpyAsync(&rc, code[cur], sizeof(int), hipMemcpyDeviceToHost, stream)) != hipSuccess) return err;
-    if ((err = hipStreamSynchronize(stream)) != hipSuccess) return err;
-    root = rc;
+    if ((err = ploc_cluster(in, morton.vals2, S, T, stream, &rc)) != hipSuccess) return err;
     if (rc < 0) {  // single triangle
-        if ((err = hipMemcpyAsync(dfs, morton_order, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream)) !=
-            hipSuccess)
-            return err;
-        root = ~0;
+        err = hipMemcpyAsync(S.dfs, morton.vals2, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+        T.root = ~0;
     } else {
-        int2 w0 = make_int2(rc, 0);
-        int nwork = 1, c = 0;
-        int* nnext = tot;
-        if ((err = hipMemcpyAsync(work[0], &w0, sizeof(int2), hipMemcpyHostToDevice, stream)) != hipSuccess)
-            return err;
-        while (nwork > 0) {
-            if ((err = hipMemsetAsync(nnext, 0, sizeof(int), stream)) != hipSuccess) return err;
-            hipLaunchKernelGGL(k_ploc_dfs, dim3(grid_for(nwork, 128)), dim3(128), 0, stream, work[c], nwork, bchild,
-                               bcount, brange, morton_order, dfs, work[c ^ 1], nnext);
-            if ((err = hipGetLastError()) != hipSuccess) return err;
-            if ((err = hipMemcpyAsync(&nwork, nnext, sizeof(int), hipMemcpyDeviceToHost, stream)) != hipSuccess)
-                return err;
-            if ((err = hipStreamSynchronize(stream)) != hipSuccess) return err;
-            c ^= 1;
+        err = ploc_number(rc, morton.vals2, S, T, stream);
+        T.root = rc;
+    }
+    if (err != hipSuccess) return err;
+    return gather_leaves(in, S.dfs, out, T, stream);
+}
+
+// The SAH front ends' common end: with the tree's nodes and the DFS triangle order `dfs` on the
+// device, the leaf gather; then a host sync, after which the caller's host arrays may go.
+hipError_t finish_sah(const BuildInput& in, const uint32_t* dfs, BuildOutput& out, BinaryTree& T, hipStream_t stream) {
+    const hipError_t err = gather_leaves(in, dfs, out, T, stream);
+    if (err != hipSuccess) return err;
+    T.root = 0;
+    return hipStreamSynchronize(stream);
+}
+
+// Host binned SAH (pt_sah.cpp), n >= 2: the tree is built on the host and uploaded.
+hipError_t build_sah_host(const BuildInput& in, BuildOutput& out, hipStream_t stream, hipEvent_t start,
+                          DevBuf<uint32_t>& dfs, BinaryTree& T) {
+    const int n = in.n;
+    const size_t nbin = (size_t)n - 1;
+    hipError_t err;
+    if ((err = hipEventRecord(start, stream)) != hipSuccess) return err;
+    std::vector<uint32_t> order;
+    std::vector<int2> hchild, hrange;
+    std::vector<float4> hbox;
+    sah_binary_tree(in.tri_host, n, order, hchild, hrange, hbox);
+    if (PT_SAH_REINSERT > 0) {
+        // kept only when it cuts the binary tree's cost by 2 % or more: Sponza-class 8.9 % ->
+        // +0.5 % Msamples/s; the sphere box 0.13 % -> one level deeper and -1.1 to -1.6 %
+        // (profiles/r04u_ab_reinsert_sponza.log)
+        std::vector<uint32_t> order2 = order;
+        std::vector<int2> child2 = hchild, range2 = hrange;
+        std::vector<float4> box2 = hbox;
+        if (sah_reinsert(order2, child2, range2, box2, in.tri_host, PT_SAH_REINSERT) >= 0.02) {
+            order.swap(order2);
+            hchild.swap(child2);
+            hrange.swap(range2);
+            hbox.swap(box2);
         }
     }
-    hipLaunchKernelGGL(k_gather, dim3(grid_for(n, 256)), dim3(256), 0, stream, in.tri_orig, in.nrm_orig, in.uv_orig, dfs,
-                       n, out.isect, out.shade, out.tuv, leafbox, pleaf);
+    if ((err = first_error({dfs.alloc(n), T.alloc(n, n)})) != hipSuccess) return err;
+    if ((err = first_error(
+             {hipMemcpyAsync(dfs, order.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, stream),
+              hipMemcpyAsync(T.child, hchild.data(), sizeof(int2) * nbin, hipMemcpyHostToDevice, stream),
+              hipMemcpyAsync(T.range, hrange.data(), sizeof(int2) * nbin, hipMemcpyHostToDevice, stream),
+              hipMemcpyAsync(T.box, hbox.data(), sizeof(float4) * 2 * nbin, hipMemcpyHostToDevice, stream)})) !=
+        hipSuccess)
+        return err;
+    return finish_sah(in, dfs, out, T, stream);
+}
+
+// The same tree built on the GPU (pt_sah_gpu.hip), n >= 2.
+hipError_t build_sah_gpu(const BuildInput& in, BuildOutput& out, hipStream_t stream, hipEvent_t start,
+                         DevBuf<uint32_t>& dfs, BinaryTree& T) {
+    const int n = in.n;
+    hipError_t err;
+    if ((err = hipEventRecord(start, stream)) != hipSuccess) return err;
+    if ((err = first_error({dfs.alloc(n), T.alloc(n, n)})) != hipSuccess) return err;
+    if ((err = sah_build_gpu(in.tri_orig, n, dfs, T.child, T.range, T.box, stream)) != hipSuccess) return err;
+    return finish_sah(in, dfs, out, T, stream);
+}
+
+// The back end's scratch: the level-by-level work lists and the scan's storage, allocated before
+// the timed window, and the SAH dynamic programme's arrays, allocated inside it (alloc_dp).
+// bvh_build releases all of it after the stop event, as it does the front ends' scratch.
+struct CollapseScratch {
+    DevBuf<int> work, work2, wcnt, woff;
+    DevBuf<unsigned char> temp;
+    size_t temp_bytes = 0;
+    DevBuf<int> parent, leafparent, visits, dec;
+    DevBuf<float4> cost;
+    hipError_t alloc(int n, hipStream_t stream) {
+        hipError_t err = first_error({work.alloc(n), work2.alloc(n), wcnt.alloc(n), woff.alloc(n)});
+        if (err != hipSuccess) return err;
+        err = hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, wcnt.get(), woff.get(), n, stream);
+        return err != hipSuccess ? err : alloc_temp(temp, temp_bytes);
+    }
+    hipError_t alloc_dp(int n, BinaryTree& T) {
+        const size_t nbin = (size_t)n - 1;
+        return first_error({parent.alloc(nbin), leafparent.alloc(n), visits.alloc(nbin), cost.alloc(nbin),
+                            dec.alloc(nbin), T.pbox.alloc(2 * nbin)});
+    }
+};
+
+// The back end, part 1: k_sah_dp picks every binary node's cheapest cover by 1-4 BVH4 children
+// (C.dec) and fills T.pbox.  Nothing to do for the tree of a single leaf: C.dec stays empty.
+hipError_t sah_dp(BinaryTree& T, int n, CollapseScratch& C, hipStream_t stream) {
+    if (T.root < 0) return hipSuccess;
+    const int nbin = n - 1;
+    hipError_t err;
+    if ((err = C.alloc_dp(n, T)) != hipSuccess) return err;
+    if ((err = hipMemsetAsync(C.visits, 0, sizeof(int) * nbin, stream)) != hipSuccess) return err;
+    if ((err = hipMemsetAsync(C.parent, 0xff, sizeof(int) * nbin, stream)) != hipSuccess) return err;  // root: -1
+    const BinTree B = T.view();
+    hipLaunchKernelGGL(k_parents, dim3(grid_for(nbin, 256)), dim3(256), 0, stream, B.child, nbin, C.parent.get(),
+                       C.leafparent.get());
     if ((err = hipGetLastError()) != hipSuccess) return err;
-    B.child = bchild;
-    B.range = brange;
-    B.box = bbox;
-    B.leafbox = leafbox;
-    B.pleaf = pleaf;
+    hipLaunchKernelGGL(k_sah_dp, dim3(grid_for(n, 256)), dim3(256), 0, stream, B, n, C.parent.get(), C.leafparent.get(),
+                       C.visits.get(), C.cost.get(), C.dec.get());
+    return hipGetLastError();
+}
+
+// The back end: the SAH dynamic programme over the binary tree, then the BVH4 nodes one level at
+// a time (count -> scan -> emit, one host sync per level), numbered breadth-first.  Fills
+// out.nodes and, on success only, out.n_nodes, out.depth and out.level_base.
+hipError_t collapse_bvh4(BinaryTree& T, int n, CollapseScratch& C, BuildOutput& out, hipStream_t stream) {
+    hipError_t err;
+    if ((err = sah_dp(T, n, C, stream)) != hipSuccess) return err;
+    const int* dec = C.dec;
+    const BinTree B = T.view();
+    int *work = C.work, *work2 = C.work2;
+    int nwork = 1, depth = 0, node_count = 1, level_base = 0;
+    std::vector<int> bases;
+    // level 0: the binary root (or the single leaf ~0) -> BVH4 slot 0
+    if ((err = hipMemcpyAsync(work, &T.root, sizeof(int), hipMemcpyHostToDevice, stream)) != hipSuccess) return err;
+    while (nwork > 0) {
+        bases.push_back(level_base);
+        hipLaunchKernelGGL(k_collapse_count, dim3(grid_for(nwork, 128)), dim3(128), 0, stream, B, dec, work,
+                           nwork, C.wcnt.get());
+        if ((err = hipGetLastError()) != hipSuccess) return err;
+        if ((err = hipcub::DeviceScan::ExclusiveSum(C.temp.get(), C.temp_bytes, C.wcnt.get(), C.woff.get(), nwork,
+                                                    stream)) != hipSuccess)
+            return err;
+        hipLaunchKernelGGL(k_collapse_emit, dim3(grid_for(nwork, 128)), dim3(128), 0, stream, B, dec, work, nwork,
+                           C.woff.get(), level_base, node_count, out.nodes, work2);
+        if ((err = hipGetLastError()) != hipSuccess) return err;
+        int tail[2] = {0, 0};  // offset and count of the level's last item: the next level's size
+        if ((err = first_error(
+                 {hipMemcpyAsync(&tail[0], C.woff + nwork - 1, sizeof(int), hipMemcpyDeviceToHost, stream),
+                  hipMemcpyAsync(&tail[1], C.wcnt + nwork - 1, sizeof(int), hipMemcpyDeviceToHost, stream),
+                  hipStreamSynchronize(stream)})) != hipSuccess)
+            return err;
+        nwork = tail[0] + tail[1];
+        level_base = node_count;
+        node_count += nwork;
+        ++depth;
+        std::swap(work, work2);
+    }
+    bases.push_back(node_count);
+    out.n_nodes = node_count;
+    out.depth = depth;
+    out.level_base.swap(bases);
     return hipSuccess;
 }
 
 }  // namespace
 
-#define PT_TRY(x)                          \
-    do {                                   \
-        hipError_t e_ = (x);               \
-        if (e_ != hipSuccess) {            \
-            err = e_;                      \
-            goto done;                     \
-        }                                  \
-    } while (0)
-
-hipError_t lbvh_build(const BuildInput& in, BuildOutput& out, hipStream_t stream, float* ms) {
+hipError_t bvh_build(const BuildInput& in, BuildOutput& out, hipStream_t stream, float* ms) {
     const int n = in.n;
-    hipError_t err = hipSuccess;
-    uint32_t *keys = nullptr, *vals = nullptr, *keys2 = nullptr, *vals2 = nullptr;
-    float4 *st = nullptr, *bbox = nullptr;
-    int2 *bchild = nullptr, *brange = nullptr;
-    int *work = nullptr, *work2 = nullptr, *wcnt = nullptr, *woff = nullptr;
-    int *dp_parent = nullptr, *dp_leafparent = nullptr, *dp_visits = nullptr, *dp_dec = nullptr;
-    float4 *dp_cost = nullptr, *lb_pleaf = nullptr, *pbox = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0, scan_bytes = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int levels = 1;
-    SparseTable table{};
-    BinTree B{};
-    int nwork = 1, depth = 0, root = 0, node_count = 1, level_base = 0;
-    const int nbin = n > 1 ? n - 1 : 1;
-    const bool ploc = in.builder != kBuilderLBVH;
-    std::vector<void*> owned;
     if (ms) *ms = 0.0f;
     out.n_nodes = 0;
     out.depth = 0;
     out.level_base.clear();
     if (n <= 0) return hipSuccess;
-    while ((1 << levels) <= n) ++levels;  // levels 0..levels-1 with 2^l <= n
-    PT_TRY(hipEventCreate(&e0));
-    PT_TRY(hipEventCreate(&e1));
-    PT_TRY(hipMalloc(&keys, sizeof(uint32_t) * n));
-    PT_TRY(hipMalloc(&vals, sizeof(uint32_t) * n));
-    PT_TRY(hipMalloc(&keys2, sizeof(uint32_t) * n));
-    PT_TRY(hipMalloc(&vals2, sizeof(uint32_t) * n));
-    if (!ploc) {
-        PT_TRY(hipMalloc(&st, sizeof(float4) * 2 * (size_t)n * (size_t)levels));
-        PT_TRY(hipMalloc(&bchild, sizeof(int2) * nbin));
-        PT_TRY(hipMalloc(&brange, sizeof(int2) * nbin));
-        PT_TRY(hipMalloc(&bbox, sizeof(float4) * 2 * nbin));
-        PT_TRY(hipMalloc(&lb_pleaf, sizeof(float4) * 2 * (size_t)n));
+    Event e0, e1;
+    MortonOrder morton;    // the front ends' scratch, each one's own
+    PlocScratch ploc;
+    DevBuf<uint32_t> dfs;  // the SAH builders' triangle order
+    CollapseScratch scratch;
+    BinaryTree tree;
+    StreamIdle idle(stream);  // declared last: the stream is idle before anything above is freed
+    hipError_t err = first_error({e0.ensure(), e1.ensure(), scratch.alloc(n, stream)});
+    if (err != hipSuccess) return err;
+    // a single triangle has no SAH split: the SAH builders take the PLOC path for it
+    switch ((n > 1 || in.builder == kBuilderLBVH) ? in.builder : kBuilderPLOC) {
+        case kBuilderLBVH: err = build_lbvh(in, out, stream, e0, morton, tree); break;
+        case kBuilderSAH: err = build_sah_host(in, out, stream, e0, dfs, tree); break;
+        case kBuilderSAHGPU: err = build_sah_gpu(in, out, stream, e0, dfs, tree); break;
+        default: err = build_ploc(in, out, stream, e0, morton, ploc, tree); break;
     }
-    PT_TRY(hipMalloc(&work, sizeof(int) * n));
-    PT_TRY(hipMalloc(&work2, sizeof(int) * n));
-    PT_TRY(hipMalloc(&wcnt, sizeof(int) * n));
-    PT_TRY(hipMalloc(&woff, sizeof(int) * n));
-    PT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys, keys2, vals, vals2, n, 0, 30, stream));
-    PT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, wcnt, woff, n, stream));
-    temp_bytes = std::max(temp_bytes, scan_bytes);
-    PT_TRY(hipMalloc(&temp, temp_bytes > 0 ? temp_bytes : 16));
-    PT_TRY(hipEventRecord(e0, stream));
-    if ((in.builder == kBuilderSAH || in.builder == kBuilderSAHGPU) && n > 1) {
-        // host binned-SAH binary tree, then the same leaf gather and SAH-optimal collapse
-        std::vector<uint32_t> order;
-        std::vector<int2> hchild, hrange;
-        std::vector<float4> hbox;
-        const bool on_gpu = in.builder == kBuilderSAHGPU;
-        if (!on_gpu) sah_binary_tree(in.tri_host, n, order, hchild, hrange, hbox);
-        if (!on_gpu && PT_SAH_REINSERT > 0) {
-            // kept only when it cuts the binary tree's cost by 2 % or more: Sponza-class 8.9 % ->
-            // +0.5 % Msamples/s; the sphere box 0.13 % -> one level deeper and -1.1 to -1.6 %
-            // (profiles/r04u_ab_reinsert_sponza.log)
-            std::vector<uint32_t> order2 = order;
-            std::vector<int2> child2 = hchild, range2 = hrange;
-            std::vector<float4> box2 = hbox;
-            if (sah_reinsert(order2, child2, range2, box2, in.tri_host, PT_SAH_REINSERT) >= 0.02) {
-                order.swap(order2);
-                hchild.swap(child2);
-                hrange.swap(range2);
-                hbox.swap(box2);
-            }
-        }
-        uint32_t* dfs = nullptr;
-        float4 *sbox = nullptr, *sleaf = nullptr, *spleaf = nullptr;
-        int2 *schild = nullptr, *srange = nullptr;
-        for (auto pr : {std::make_pair((void**)&dfs, sizeof(uint32_t) * (size_t)n),
-                        std::make_pair((void**)&schild, sizeof(int2) * (size_t)nbin),
-                        std::make_pair((void**)&srange, sizeof(int2) * (size_t)nbin),
-                        std::make_pair((void**)&sbox, sizeof(float4) * 2 * (size_t)nbin),
-                        std::make_pair((void**)&sleaf, sizeof(float4) * 2 * (size_t)n),
-                        std::make_pair((void**)&spleaf, sizeof(float4) * 2 * (size_t)n)}) {
-            PT_TRY(hipMalloc(pr.first, pr.second));
-            owned.push_back(*pr.first);
-        }
-        if (on_gpu) {
-            PT_TRY(sah_build_gpu(in.tri_orig, n, dfs, schild, srange, sbox, stream));
-        } else {
-            PT_TRY(hipMemcpyAsync(dfs, order.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, stream));
-            PT_TRY(hipMemcpyAsync(schild, hchild.data(), sizeof(int2) * (size_t)nbin, hipMemcpyHostToDevice, stream));
-            PT_TRY(hipMemcpyAsync(srange, hrange.data(), sizeof(int2) * (size_t)nbin, hipMemcpyHostToDevice, stream));
-            PT_TRY(hipMemcpyAsync(sbox, hbox.data(), sizeof(float4) * 2 * (size_t)nbin, hipMemcpyHostToDevice, stream));
-        }
-        hipLaunchKernelGGL(k_gather, dim3(grid_for(n, 256)), dim3(256), 0, stream, in.tri_orig, in.nrm_orig,
-                           in.uv_orig, dfs, n, out.isect, out.shade, out.tuv, sleaf, spleaf);
-        PT_TRY(hipGetLastError());
-        PT_TRY(hipStreamSynchronize(stream));  // the host vectors go out of scope
-        B.child = schild;
-        B.range = srange;
-        B.box = sbox;
-        B.leafbox = sleaf;
-        B.pleaf = spleaf;
-        root = 0;
+    if (err == hipSuccess) err = collapse_bvh4(tree, n, scratch, out, stream);
+    if (err == hipSuccess) err = hipEventRecord(e1, stream);
+    if (err == hipSuccess) err = hipEventSynchronize(e1);
+    if (err == hipSuccess && ms) err = hipEventElapsedTime(ms, e0, e1);
+    if (err != hipSuccess) {
+        out.n_nodes = 0;
+        out.depth = 0;
+        out.level_base.clear();
     }
-    if ((in.builder != kBuilderSAH && in.builder != kBuilderSAHGPU) || n <= 1) {
-        float3 cmin = make_float3(in.cmin[0], in.cmin[1], in.cmin[2]);
-        float ex = in.cmax[0] - in.cmin[0], ey = in.cmax[1] - in.cmin[1], ez = in.cmax[2] - in.cmin[2];
-        float3 cinv = make_float3(ex > 0.0f ? 1.0f / ex : 0.0f, ey > 0.0f ? 1.0f / ey : 0.0f,
-                                  ez > 0.0f ? 1.0f / ez : 0.0f);
-        hipLaunchKernelGGL(k_morton, dim3(grid_for(n, 256)), dim3(256), 0, stream, in.tri_orig, n, cmin, cinv, keys,
-                           vals);
-        PT_TRY(hipGetLastError());
-        PT_TRY(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys2, vals, vals2, n, 0, 30, stream));
-        if (ploc) {
-            PT_TRY(ploc_build(in, vals2, out, stream, B, root, owned));
-        } else {
-            hipLaunchKernelGGL(k_gather, dim3(grid_for(n, 256)), dim3(256), 0, stream, in.tri_orig, in.nrm_orig,
-                               in.uv_orig, vals2, n, out.isect, out.shade, out.tuv, st, lb_pleaf);
-            PT_TRY(hipGetLastError());
-            table.n = n;
-            table.level[0] = st;
-            for (int l = 1; l < levels; ++l) {
-                float4* prev = st + 2 * (size_t)n * (size_t)(l - 1);
-                float4* cur = st + 2 * (size_t)n * (size_t)l;
-                int count = n - (1 << l) + 1;
-                hipLaunchKernelGGL(k_sparse, dim3(grid_for(count, 256)), dim3(256), 0, stream, prev, cur, count,
-                                   1 << (l - 1));
-                PT_TRY(hipGetLastError());
-                table.level[l] = cur;
-            }
-            if (n > 1) {
-                hipLaunchKernelGGL(k_karras, dim3(grid_for(n - 1, 256)), dim3(256), 0, stream, keys2, n, table,
-                                   bchild, brange, bbox);
-                PT_TRY(hipGetLastError());
-            }
-            B.child = bchild;
-            B.range = brange;
-            B.box = bbox;
-            B.leafbox = st;
-            B.pleaf = lb_pleaf;
-            root = n > 1 ? 0 : ~0;
-        }
-    }
-    {
-        if (root >= 0) {  // SAH DP over the binary tree (n >= 2)
-            PT_TRY(hipMalloc(&dp_parent, sizeof(int) * nbin));
-            PT_TRY(hipMalloc(&dp_leafparent, sizeof(int) * n));
-            PT_TRY(hipMalloc(&dp_visits, sizeof(int) * nbin));
-            PT_TRY(hipMalloc(&dp_cost, sizeof(float4) * nbin));
-            PT_TRY(hipMalloc(&dp_dec, sizeof(int) * nbin));
-            PT_TRY(hipMalloc(&pbox, sizeof(float4) * 2 * nbin));
-            B.pbox = pbox;
-            PT_TRY(hipMemsetAsync(dp_visits, 0, sizeof(int) * nbin, stream));
-            PT_TRY(hipMemsetAsync(dp_parent, 0xff, sizeof(int) * nbin, stream));  // root: -1
-            hipLaunchKernelGGL(k_parents, dim3(grid_for(nbin, 256)), dim3(256), 0, stream, B.child, nbin, dp_parent,
-                               dp_leafparent);
-            PT_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sah_dp, dim3(grid_for(n, 256)), dim3(256), 0, stream, B, n, dp_parent, dp_leafparent,
-                               dp_visits, dp_cost, dp_dec);
-            PT_TRY(hipGetLastError());
-        }
-        // level 0: the binary root (or the single leaf ~0) -> BVH4 slot 0
-        PT_TRY(hipMemcpyAsync(work, &root, sizeof(int), hipMemcpyHostToDevice, stream));
-        while (nwork > 0) {
-            out.level_base.push_back(level_base);
-            hipLaunchKernelGGL(k_collapse_count, dim3(grid_for(nwork, 128)), dim3(128), 0, stream, B, dp_dec, work,
-                               nwork, wcnt);
-            PT_TRY(hipGetLastError());
-            PT_TRY(hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, wcnt, woff, nwork, stream));
-            hipLaunchKernelGGL(k_collapse_emit, dim3(grid_for(nwork, 128)), dim3(128), 0, stream, B, dp_dec, work,
-                               nwork, woff, level_base, node_count, out.nodes, work2);
-            PT_TRY(hipGetLastError());
-            int tail[2] = {0, 0};  // offset and count of the level's last item: the next level's size
-            PT_TRY(hipMemcpyAsync(&tail[0], woff + nwork - 1, sizeof(int), hipMemcpyDeviceToHost, stream));
-            PT_TRY(hipMemcpyAsync(&tail[1], wcnt + nwork - 1, sizeof(int), hipMemcpyDeviceToHost, stream));
-            PT_TRY(hipStreamSynchronize(stream));
-            nwork = tail[0] + tail[1];
-            level_base = node_count;
-            node_count += nwork;
-            ++depth;
-            std::swap(work, work2);
-        }
-    }
-    PT_TRY(hipEventRecord(e1, stream));
-    PT_TRY(hipEventSynchronize(e1));
-    if (ms) PT_TRY(hipEventElapsedTime(ms, e0, e1));
-    out.n_nodes = node_count;
-    out.depth = depth;
-    out.level_base.push_back(node_count);
-done:
-    (void)hipStreamSynchronize(stream);
-    for (void* p : {(void*)keys, (void*)vals, (void*)keys2, (void*)vals2, (void*)st, (void*)bchild, (void*)brange,
-                    (void*)bbox, (void*)work, (void*)work2, (void*)wcnt, (void*)woff, temp, (void*)dp_parent,
-                    (void*)dp_leafparent, (void*)dp_visits, (void*)dp_cost, (void*)dp_dec, (void*)lb_pleaf,
-                    (void*)pbox})
-        if (p) (void)hipFree(p);
-    for (void* p : owned) (void)hipFree(p);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     return err;
 }
 

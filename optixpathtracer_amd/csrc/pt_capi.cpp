@@ -1,6 +1,6 @@
 // pt_capi.cpp — the C ABI of libptamd.so (include/ptamd.h): host driver for the gfx950
 // path tracer.  Replaces Renderer/OptiX/OptixRenderer.{h,cpp} of Damo12320/OptixPathtracer
-// (context/module/pipeline/SBT setup collapse into: upload scene -> LBVH build -> launch).
+// (context/module/pipeline/SBT setup collapse into: upload scene -> BVH build -> launch).
 //
 // There is no CPU fallback: every render and trace call runs the HIP kernels or fails
 // with a negative status.
@@ -24,11 +24,6 @@ int hip_fail(hipError_t e, const char* where) {
 }
 
 }  // namespace pt
-
-pt_renderer::~pt_renderer() {
-    wavefront_free(wf);
-    for (int k = 1; k < kMaxWFStreams; ++k) wavefront_free(xwf[k]);
-}
 
 namespace {
 

@@ -63,7 +63,7 @@ static int ahead_frames(pt_renderer* r, size_t n3, bool by_time) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b > 0) {
         size_t held = 2 * sizeof(float) * n3 * (size_t)std::max(r->ahead.ring[0].cap(n3), r->ahead.ring[1].cap(n3));
-        if (r->wf.paths > 0) held += wavefront_bytes(r->wf.paths, r->wf.max_bounces);
+        if (r->wf.paths() > 0) held += wavefront_bytes(r->wf.paths(), r->wf.max_bounces());
         const size_t avail = std::min(total_b / 4, free_b + held);
         k = std::min<size_t>((size_t)k, std::max<size_t>(1, avail / per_frame));
     } else {

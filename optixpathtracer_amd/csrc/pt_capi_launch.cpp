@@ -77,9 +77,9 @@ namespace pt {
 
 // Bytes the wavefront queues of all streams hold now.
 size_t queue_bytes_held(const pt_renderer* r) {
-    size_t b = r->wf.paths > 0 ? wavefront_bytes(r->wf.paths, r->wf.max_bounces) : 0;
+    size_t b = r->wf.paths() > 0 ? wavefront_bytes(r->wf.paths(), r->wf.max_bounces()) : 0;
     for (int k = 1; k < pt_renderer::kMaxWFStreams; ++k)
-        if (r->xwf[k].paths > 0) b += wavefront_bytes(r->xwf[k].paths, r->xwf[k].max_bounces);
+        if (r->xwf[k].paths() > 0) b += wavefront_bytes(r->xwf[k].paths(), r->xwf[k].max_bounces());
     return b;
 }
 
@@ -118,26 +118,26 @@ int reserve_queues(pt_renderer* r, WFPlan* plan, size_t budget, int P) {
     const int maxb = std::max(1, r->max_bounces);
     int& nf_cap = plan->nf_cap;
     for (int k = 0; k < plan->ns; ++k) {
-        WFState& w = k ? r->xwf[k] : r->wf;
+        WFQueues& w = k ? r->xwf[k] : r->wf;
         // queues larger than the budget's share (a lowered budget) are allocated again, smaller
         // (a budget below one frame's queues still allows one frame: no reallocation per call)
-        const bool over = budget != SIZE_MAX && w.paths > P &&
-                          (size_t)plan->ns * wavefront_bytes(w.paths, w.max_bounces) > budget;
-        if (w.paths < P * nf_cap || w.max_bounces < r->max_bounces || over) {
+        const bool over = budget != SIZE_MAX && w.paths() > P &&
+                          (size_t)plan->ns * wavefront_bytes(w.paths(), w.max_bounces()) > budget;
+        if (w.paths() < P * nf_cap || w.max_bounces() < r->max_bounces || over) {
             for (int j = 0; j < pt_renderer::kMaxWFStreams; ++j)
                 if (r->wf_stream(j)) PT_HIP(hipStreamSynchronize(r->wf_stream(j)), "hipStreamSynchronize");
-            wavefront_free(w);
-            hipError_t ae = wavefront_alloc(w, P * nf_cap, maxb);
+            w.release();
+            hipError_t ae = w.alloc(P * nf_cap, maxb);
             if (ae == hipErrorOutOfMemory && k == 0) {
                 // queues of the other streams (an earlier call's, or a mode with more
                 // streams) go first, then the full batch again
                 bool freed = false;
                 for (int j = 1; j < pt_renderer::kMaxWFStreams; ++j)
-                    if (r->xwf[j].paths > 0) {
-                        wavefront_free(r->xwf[j]);
+                    if (r->xwf[j].paths() > 0) {
+                        r->xwf[j].release();
                         freed = true;
                     }
-                if (freed) ae = wavefront_alloc(w, P * nf_cap, maxb);
+                if (freed) ae = w.alloc(P * nf_cap, maxb);
             }
             // the first stream's queues: halve the batch until they fit (every batch size gives
             // the same image), PT_ERR_NOMEM only when one frame does not; the size that fitted
@@ -146,7 +146,7 @@ int reserve_queues(pt_renderer* r, WFPlan* plan, size_t budget, int P) {
             while (ae == hipErrorOutOfMemory && k == 0 && nf_cap > 1) {
                 nf_cap = (nf_cap + 1) / 2;
                 r->nf_fit = nf_cap;
-                ae = wavefront_alloc(w, P * nf_cap, maxb);
+                ae = w.alloc(P * nf_cap, maxb);
             }
             // the extra streams only overlap batches: when their queues do not fit, render on
             // the k streams that do (the image is the same, added in frame order either way)
@@ -154,7 +154,7 @@ int reserve_queues(pt_renderer* r, WFPlan* plan, size_t budget, int P) {
                 plan->ns = k;
                 break;
             }
-            PT_HIP(ae, "wavefront_alloc");
+            PT_HIP(ae, "WFQueues::alloc");
         }
     }
     return PT_OK;
@@ -208,14 +208,14 @@ int plan_wavefront(pt_renderer* r, uint32_t n, WFPlan* plan, int P, bool mapped)
         nf_cap = std::min(nf_cap, nf_b);
         size_t used = (size_t)ns * wavefront_bytes(P * nf_cap, maxb);
         for (int k = ns; k < pt_renderer::kMaxWFStreams; ++k) {
-            if (r->xwf[k].paths == 0) continue;
-            const size_t held = wavefront_bytes(r->xwf[k].paths, r->xwf[k].max_bounces);
+            if (r->xwf[k].paths() == 0) continue;
+            const size_t held = wavefront_bytes(r->xwf[k].paths(), r->xwf[k].max_bounces());
             if (used + held <= budget) {
                 used += held;
                 continue;
             }
             PT_HIP(hipStreamSynchronize(r->xstream[k]), "hipStreamSynchronize");
-            wavefront_free(r->xwf[k]);
+            r->xwf[k].release();
         }
     }
     plan->nf_cap = nf_cap;
@@ -246,7 +246,7 @@ int fork_resources(pt_renderer* r, int ns, int nband) {
 
 // The queues of stream sk for one batch; a speculative batch also carries the cancel words.
 WFState batch_queues(pt_renderer* r, int sk, bool speculative, bool first_batch) {
-    WFState wq = sk ? r->xwf[sk] : r->wf;
+    WFState wq = (sk ? r->xwf[sk] : r->wf).state();
     if (speculative && r->ahead.d_cancel_seen) {  // a look-ahead batch: its kernels poll the cancel words
         wq.cancel_host = r->ahead.cancel.d;
         wq.cancel_seen = r->ahead.d_cancel_seen;

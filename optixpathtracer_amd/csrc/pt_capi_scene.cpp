@@ -50,10 +50,10 @@ int build_tree(pt_renderer* r, const std::vector<float4>& tri, const std::vector
             in.cmin[a] = cmin[a];
             in.cmax[a] = cmax[a];
         }
-        e = lbvh_build(in, bo, r->stream, &ms);
+        e = bvh_build(in, bo, r->stream, &ms);
     }
     (void)hipStreamSynchronize(r->stream);
-    if (e != hipSuccess) return hip_fail(e, "lbvh_build");
+    if (e != hipSuccess) return hip_fail(e, "bvh_build");
     if (ms_out) *ms_out = ms;
     else r->timing.bvh_ms = ms;
     return PT_OK;

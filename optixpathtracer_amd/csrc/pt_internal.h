@@ -25,7 +25,8 @@ struct BuildInput {
     const float4* uv_orig;   // 2 per triangle (uv0, uv1 | uv2, 0) or NULL (no textures)
     int n;
     float cmin[3], cmax[3];  // centroid bounds (Morton quantisation range)
-    int builder;             // kBuilderPLOC (default), kBuilderLBVH or kBuilderSAH
+    int builder;             // kBuilder*: the front end that makes the binary tree (pt_create's default
+                             // is kBuilderSAHGPU); any other value builds with PLOC
     const float4* tri_host;  // the same triangles on the host (kBuilderSAH builds there)
 };
 constexpr int kBuilderPLOC = 0;
@@ -52,13 +53,13 @@ hipError_t sah_build_gpu(const float4* tri, int n, uint32_t* order, int2* child,
 double sah_reinsert(std::vector<uint32_t>& order, std::vector<int2>& child, std::vector<int2>& range,
                     std::vector<float4>& box, const float4* tri, int rounds);
 
-// BVH4 (collapsed LBVH) + triangle records in leaf order.
+// BVH4 (the SAH-optimal collapse of the builder's binary tree) + triangle records in leaf order.
 struct BuildOutput {
     BNode4* nodes;  // capacity max(1, n) nodes
     float4* isect;  // 3n
     float4* shade;  // 4n
     float4* tuv;    // 2n or NULL
-    int n_nodes;    // written by lbvh_build
+    int n_nodes;    // written by bvh_build; 0 after a failed build
     int depth;      // BVH4 levels
     // first node of every BVH4 level (breadth-first numbering) and, last, n_nodes: level l is
     // nodes level_base[l] .. level_base[l + 1] - 1 (refit_levels walks them deepest first)
@@ -73,10 +74,11 @@ struct BuildOutput {
 constexpr float kSahCNode = 1.0f;
 constexpr float kSahCTri = PT_SAH_CTRI;
 
-// GPU LBVH build (Morton codes -> radix sort -> Karras 2012 hierarchy -> AABBs from a sparse
-// table over the sorted leaves).  Replaces optixAccelBuild (OptixRenderer.cpp:306-456).
+// GPU BVH build (pt_build.hip): in.builder's front end makes a binary tree and puts the triangle
+// records in leaf order, then the common back end collapses the tree into the BVH4.  Replaces
+// optixAccelBuild (OptixRenderer.cpp:306-456).
 // Returns hipSuccess or the first error; *ms = device time of the build.
-hipError_t lbvh_build(const BuildInput& in, BuildOutput& out, hipStream_t stream, float* ms);
+hipError_t bvh_build(const BuildInput& in, BuildOutput& out, hipStream_t stream, float* ms);
 
 // Wavefront path state: SoA queues in HBM, capacity = paths (one path per pixel per frame).
 struct WFState {
@@ -109,9 +111,26 @@ struct WFState {
     // which returns once the batch is cancelled, the word is set, or 10 s have passed
     const unsigned* hold_release = nullptr;
 };
+// Bytes of a queue set: the sum over the table of its arrays (pt_wavefront.hip kQueueArrays).
 size_t wavefront_bytes(int paths, int max_bounces);
-hipError_t wavefront_alloc(WFState& W, int paths, int max_bounces);
-void wavefront_free(WFState& W);
+// Owner of a queue set's arrays: frees them in its destructor and hands out the WFState the kernels
+// take by value.  alloc and release walk the same table as wavefront_bytes.
+class WFQueues {
+    WFState w_;
+
+public:
+    WFQueues() = default;
+    WFQueues(const WFQueues&) = delete;
+    WFQueues& operator=(const WFQueues&) = delete;
+    ~WFQueues() { release(); }
+    // Releases what it held first.  No partial queue set survives a failed allocation: paths() stays
+    // 0, so the next launch_frames allocates again instead of launching on null queues.
+    hipError_t alloc(int paths, int max_bounces);
+    void release();
+    const WFState& state() const { return w_; }
+    int paths() const { return w_.paths; }
+    int max_bounces() const { return w_.max_bounces; }
+};
 // pt_set_kernel_timing: the pools whose event pairs bracket a batch's k_extend launches, its
 // k_trace_pair launches and the dominant shading launch of each bounce (k_shade_fused / k_shade0_pixel
 // in the fused modes, k_shade_nee in Default / Layered).  The launcher draws a pair at the launch it

@@ -155,7 +155,7 @@ struct pt_renderer {
     static constexpr int kMaxWFStreams = 4;
     int wf_streams = 0;  // 0 = auto (launch_frames): two for Conductor and Dielectric, one otherwise
     pt::Stream xstream[kMaxWFStreams];  // [0] unused: stream 0 is `stream`
-    pt::WFState xwf[kMaxWFStreams];     // [0] unused: stream 0's queues are `wf`
+    pt::WFQueues xwf[kMaxWFStreams];    // [0] unused: stream 0's queues are `wf`
     pt::Event ev_fork, ev_join[kMaxWFStreams], ev_accum[2];
     hipStream_t wf_stream(int k) const { return k ? xstream[k] : stream; }
     // scene
@@ -164,7 +164,7 @@ struct pt_renderer {
     pt::DevBuf<float4> d_shade;
     int bvh_nodes = 0, bvh_depth = 0;
     bool trav_stats = false;
-    pt::WFState wf;
+    pt::WFQueues wf;
     pt::DevBuf<float4> d_mats;
     int ntri = 0;
     int nmesh = 0;
@@ -445,8 +445,7 @@ struct pt_renderer {
         bool active() const { return set.supersample > 1 || R > 0; }
     } filter;
 
-    pt_renderer() = default;
-    ~pt_renderer();  // the queue sets (wavefront_free); everything else releases itself
+    pt_renderer() = default;  // no destructor: every member releases what it holds
     pt::DevScene scene() const {
         pt::DevScene S;
         S.nodes = d_nodes;

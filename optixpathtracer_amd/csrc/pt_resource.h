@@ -1,9 +1,11 @@
-// pt_resource.h — owners of the HIP resources the C-ABI driver (pt_capi*.cpp) holds: each releases
-// what it holds in its destructor, none can be copied.  Not part of the public ABI.
+// pt_resource.h — owners of the HIP resources the host code holds, the C-ABI driver (pt_capi*.cpp)
+// and the BVH builders' host stages (pt_build.hip, pt_sah_gpu.hip) alike: each releases what it holds
+// in its destructor, none can be copied.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <utility>
 #include <vector>
 
@@ -46,6 +48,23 @@ public:
         std::swap(p_, o.p_);
         std::swap(n_, o.n_);
     }
+};
+
+// The first failure among results listed in order, e.g. first_error({a.alloc(n), b.alloc(n)}).
+inline hipError_t first_error(std::initializer_list<hipError_t> results) {
+    for (hipError_t e : results)
+        if (e != hipSuccess) return e;
+    return hipSuccess;
+}
+
+// Waits for `s` when it goes out of scope.  Declared after a function's scratch buffers it is
+// destroyed before them, so on every return path the stream is idle when they are freed.
+struct StreamIdle {
+    hipStream_t s;
+    explicit StreamIdle(hipStream_t stream) : s(stream) {}
+    StreamIdle(const StreamIdle&) = delete;
+    StreamIdle& operator=(const StreamIdle&) = delete;
+    ~StreamIdle() { (void)hipStreamSynchronize(s); }
 };
 
 // The adaptive sampler's device state (pt_render_adaptive, pt_internal.h AdaptiveBuffers): the

@@ -1,6 +1,6 @@
 // pt_sah.cpp — host-side binned-SAH binary BVH over the scene triangles (pt_options.bvh_builder =
 // PT_BVH_SAH), handed to the same GPU SAH-optimal BVH4 collapse as the PLOC and LBVH trees
-// (pt_build.hip lbvh_build).  Replaces optixAccelBuild (OptixRenderer.cpp:306-456) like the
+// (pt_build.hip bvh_build).  Replaces optixAccelBuild (OptixRenderer.cpp:306-456) like the
 // other builders: the scene is static, so a slower, top-down build that splits every node at the
 // surface-area-heuristic minimum over 64 bins per axis trades pt_create time for fewer node
 // visits per ray.  Which tree is traversed never changes an image (the closest hit is the

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "pt_internal.h"
+#include "pt_resource.h"
 
 namespace pt {
 
@@ -571,140 +572,138 @@ __global__ __launch_bounds__(kSmallBlock) void k_sah_small(SahTris T, SahOut O, 
     }
 }
 
+// sah_build_gpu's device scratch: the triangles' boxes and centroids, the two triangle-index buffers
+// the levels partition between, and a large level's nodes, chunks and per-node / per-chunk results.
+struct SahScratch {
+    DevBuf<float4> tlo, thi, cen;
+    DevBuf<uint32_t> buf[2];
+    DevBuf<int> mid, code, acc, bins, cleft;
+    DevBuf<LargeNode> large;
+    DevBuf<Chunk> chunks;
+    hipError_t alloc(int n) {
+        // a level holds at most n / (kSmallMax + 1) nodes, and a node of m triangles m / kChunk + 1 chunks
+        const size_t max_nodes = (size_t)n / (kSmallMax + 1) + 1, max_chunks = (size_t)n / kChunk + max_nodes;
+        return first_error({tlo.alloc(n), thi.alloc(n), cen.alloc(n), buf[0].alloc(n), buf[1].alloc(n),
+                            mid.alloc(max_nodes), code.alloc(max_nodes), acc.alloc(kAcc * max_nodes),
+                            bins.alloc(kBinInts * max_nodes), large.alloc(max_nodes), chunks.alloc(max_chunks),
+                            cleft.alloc(max_chunks)});
+    }
+};
+
+// The large levels, top down from the root, while a node has more than kSmallMax triangles: every
+// level's nodes are split by one chain of launches and one host sync.  Leaves `small`, the subtrees
+// one wave each builds, and `fix`, the large nodes' child codes.
+hipError_t sah_large_levels(const SahTris& T, const SahOut& O, SahScratch& D, int n, std::vector<SmallTree>& small,
+                            std::vector<int2>& fix, hipStream_t stream) {
+    hipError_t err = hipSuccess;
+    std::vector<LargeNode> level;
+    std::vector<Chunk> chunks;
+    std::vector<int> mids;
+    int next_id = 1, parity = 0;
+    if (n > kSmallMax) level.push_back(LargeNode{0, n, 0, 0});
+    else small.push_back(SmallTree{0, n, 0, 0});
+    while (!level.empty()) {
+        const int nn = (int)level.size();
+        chunks.clear();
+        for (int i = 0; i < nn; ++i) {
+            level[i].chunk0 = (int)chunks.size();
+            for (int b = level[i].begin; b < level[i].end; b += kChunk)
+                chunks.push_back(Chunk{i, b, std::min(level[i].end, b + kChunk)});
+        }
+        const int nc = (int)chunks.size();
+        if ((err = hipMemcpyAsync(D.large, level.data(), sizeof(LargeNode) * nn, hipMemcpyHostToDevice, stream)) !=
+                hipSuccess ||
+            (err = hipMemcpyAsync(D.chunks, chunks.data(), sizeof(Chunk) * nc, hipMemcpyHostToDevice, stream)) !=
+                hipSuccess)
+            return err;
+        const uint32_t* src = D.buf[parity];
+        uint32_t* dst = D.buf[1 - parity];
+        int *d_acc = D.acc, *d_bins = D.bins, *d_code = D.code, *d_cleft = D.cleft, *d_mid = D.mid;
+        const LargeNode* d_large = D.large;
+        const Chunk* d_chunks = D.chunks;
+        hipLaunchKernelGGL(k_lg_init, dim3((nn * kBinInts + 255) / 256), dim3(256), 0, stream, nn, d_acc, d_bins);
+        hipLaunchKernelGGL(k_lg_bounds, dim3(nc), dim3(kChunkBlock), 0, stream, T, d_chunks, src, d_acc);
+        hipLaunchKernelGGL(k_lg_bins, dim3(nc), dim3(kChunkBlock), 0, stream, T, d_chunks, src, d_acc, d_bins);
+        hipLaunchKernelGGL(k_lg_sweep, dim3((nn + 3) / 4), dim3(256), 0, stream, O, d_large, nn, d_acc, d_bins, d_code);
+        hipLaunchKernelGGL(k_lg_count, dim3(nc), dim3(kChunkBlock), 0, stream, T, d_chunks, src, d_acc, d_code,
+                           d_cleft);
+        hipLaunchKernelGGL(k_lg_scatter, dim3(nc), dim3(kChunkBlock), 0, stream, T, d_large, d_chunks, src, dst, d_acc,
+                           d_code, d_cleft, d_mid);
+        if ((err = hipGetLastError()) != hipSuccess) return err;
+        mids.resize(nn);
+        if ((err = hipMemcpyAsync(mids.data(), d_mid, sizeof(int) * nn, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+            return err;
+        if ((err = hipStreamSynchronize(stream)) != hipSuccess) return err;
+        // every node of the level was partitioned into buf[1 - parity] (a middle cut copies)
+        std::vector<LargeNode> next;
+        for (int i = 0; i < nn; ++i) {
+            const LargeNode& nd = level[i];
+            const int b0[2] = {nd.begin, mids[i]}, e0[2] = {mids[i], nd.end};
+            int codes[2];
+            for (int s = 0; s < 2; ++s) {
+                const int sz = e0[s] - b0[s];
+                if (sz == 1) {
+                    codes[s] = ~b0[s];
+                    small.push_back(SmallTree{b0[s], e0[s], -1, 1 - parity});
+                } else if (sz > kSmallMax) {
+                    codes[s] = next_id++;
+                    next.push_back(LargeNode{b0[s], e0[s], codes[s], 0});
+                } else {
+                    codes[s] = next_id;
+                    small.push_back(SmallTree{b0[s], e0[s], next_id, 1 - parity});
+                    next_id += sz - 1;
+                }
+            }
+            fix.push_back(make_int2(nd.id, 0));
+            fix.push_back(make_int2(codes[0], codes[1]));
+        }
+        level.swap(next);
+        parity = 1 - parity;
+    }
+    return hipSuccess;
+}
+
 }  // namespace
 
 hipError_t sah_build_gpu(const float4* tri, int n, uint32_t* order, int2* child, int2* range, float4* box,
                          hipStream_t stream) {
     if (n < 2) return hipSuccess;
-    hipError_t err = hipSuccess;
-    float4 *tlo = nullptr, *thi = nullptr, *cen = nullptr;
-    uint32_t *buf[2] = {nullptr, nullptr};
-    LargeNode* d_large = nullptr;
-    Chunk* d_chunks = nullptr;
-    SmallTree* d_small = nullptr;
-    int *d_mid = nullptr, *d_acc = nullptr, *d_bins = nullptr, *d_code = nullptr, *d_cleft = nullptr;
-    int2* d_fix = nullptr;
-    std::vector<LargeNode> level;
-    std::vector<Chunk> chunks;
+    SahScratch D;
+    DevBuf<int2> d_fix;
+    DevBuf<SmallTree> d_small;
+    StreamIdle idle(stream);
     std::vector<SmallTree> small;
-    std::vector<int> mids;
     std::vector<int2> fix;  // per large node: (id, 0), (child code 0, child code 1), written at the end
-    int next_id = 1, parity = 0;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (err == hipSuccess) err = hipMalloc(p, bytes);
-    };
-    alloc((void**)&tlo, sizeof(float4) * (size_t)n);
-    alloc((void**)&thi, sizeof(float4) * (size_t)n);
-    alloc((void**)&cen, sizeof(float4) * (size_t)n);
-    alloc((void**)&buf[0], sizeof(uint32_t) * (size_t)n);
-    alloc((void**)&buf[1], sizeof(uint32_t) * (size_t)n);
-    {
-        // a level holds at most n / (kSmallMax + 1) nodes, and a node of m triangles m / kChunk + 1 chunks
-        const size_t max_nodes = (size_t)n / (kSmallMax + 1) + 1, max_chunks = (size_t)n / kChunk + max_nodes;
-        alloc((void**)&d_mid, sizeof(int) * max_nodes);
-        alloc((void**)&d_code, sizeof(int) * max_nodes);
-        alloc((void**)&d_acc, sizeof(int) * kAcc * max_nodes);
-        alloc((void**)&d_bins, sizeof(int) * kBinInts * max_nodes);
-        alloc((void**)&d_large, sizeof(LargeNode) * max_nodes);
-        alloc((void**)&d_chunks, sizeof(Chunk) * max_chunks);
-        alloc((void**)&d_cleft, sizeof(int) * max_chunks);
+    hipError_t err;
+    if ((err = D.alloc(n)) != hipSuccess) return err;
+    hipLaunchKernelGGL(k_sah_prep, dim3((n + 255) / 256), dim3(256), 0, stream, tri, n, D.tlo.get(), D.thi.get(),
+                       D.cen.get(), D.buf[0].get());
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    const SahTris T{D.tlo, D.thi, D.cen};
+    const SahOut O{child, range, box, order};
+    if ((err = sah_large_levels(T, O, D, n, small, fix, stream)) != hipSuccess) return err;
+    // a large level's node ids were handed out before the small subtrees that follow it, so the
+    // subtrees' ranges [id, id + size - 1) and the large ids never overlap (the total is n - 1)
+    if (!fix.empty()) {
+        if ((err = d_fix.alloc(fix.size())) != hipSuccess) return err;
+        if ((err = hipMemcpyAsync(d_fix, fix.data(), sizeof(int2) * fix.size(), hipMemcpyHostToDevice, stream)) !=
+            hipSuccess)
+            return err;
+        const int nf = (int)fix.size() / 2;
+        hipLaunchKernelGGL(k_sah_fix, dim3((nf + 255) / 256), dim3(256), 0, stream, d_fix.get(), nf, child);
+        if ((err = hipGetLastError()) != hipSuccess) return err;
     }
-    if (err != hipSuccess) goto done;
-    hipLaunchKernelGGL(k_sah_prep, dim3((n + 255) / 256), dim3(256), 0, stream, tri, n, tlo, thi, cen, buf[0]);
-    if ((err = hipGetLastError()) != hipSuccess) goto done;
-    {
-        const SahTris T{tlo, thi, cen};
-        const SahOut O{child, range, box, order};
-        if (n > kSmallMax) level.push_back(LargeNode{0, n, 0, 0});
-        else small.push_back(SmallTree{0, n, 0, 0});
-        while (!level.empty()) {
-            const int nn = (int)level.size();
-            chunks.clear();
-            for (int i = 0; i < nn; ++i) {
-                level[i].chunk0 = (int)chunks.size();
-                for (int b = level[i].begin; b < level[i].end; b += kChunk)
-                    chunks.push_back(Chunk{i, b, std::min(level[i].end, b + kChunk)});
-            }
-            const int nc = (int)chunks.size();
-            if ((err = hipMemcpyAsync(d_large, level.data(), sizeof(LargeNode) * nn, hipMemcpyHostToDevice, stream)) !=
-                    hipSuccess ||
-                (err = hipMemcpyAsync(d_chunks, chunks.data(), sizeof(Chunk) * nc, hipMemcpyHostToDevice, stream)) !=
-                    hipSuccess)
-                goto done;
-            const uint32_t* src = buf[parity];
-            uint32_t* dst = buf[1 - parity];
-            hipLaunchKernelGGL(k_lg_init, dim3((nn * kBinInts + 255) / 256), dim3(256), 0, stream, nn, d_acc, d_bins);
-            hipLaunchKernelGGL(k_lg_bounds, dim3(nc), dim3(kChunkBlock), 0, stream, T, d_chunks, src, d_acc);
-            hipLaunchKernelGGL(k_lg_bins, dim3(nc), dim3(kChunkBlock), 0, stream, T, d_chunks, src, d_acc, d_bins);
-            hipLaunchKernelGGL(k_lg_sweep, dim3((nn + 3) / 4), dim3(256), 0, stream, O, d_large, nn, d_acc, d_bins,
-                               d_code);
-            hipLaunchKernelGGL(k_lg_count, dim3(nc), dim3(kChunkBlock), 0, stream, T, d_chunks, src, d_acc, d_code,
-                               d_cleft);
-            hipLaunchKernelGGL(k_lg_scatter, dim3(nc), dim3(kChunkBlock), 0, stream, T, d_large, d_chunks, src, dst,
-                               d_acc, d_code, d_cleft, d_mid);
-            if ((err = hipGetLastError()) != hipSuccess) goto done;
-            mids.resize(nn);
-            if ((err = hipMemcpyAsync(mids.data(), d_mid, sizeof(int) * nn, hipMemcpyDeviceToHost, stream)) != hipSuccess)
-                goto done;
-            if ((err = hipStreamSynchronize(stream)) != hipSuccess) goto done;
-            // every node of the level was partitioned into buf[1 - parity] (a middle cut copies)
-            std::vector<LargeNode> next;
-            for (int i = 0; i < nn; ++i) {
-                const LargeNode& nd = level[i];
-                const int b0[2] = {nd.begin, mids[i]}, e0[2] = {mids[i], nd.end};
-                int codes[2];
-                for (int s = 0; s < 2; ++s) {
-                    const int sz = e0[s] - b0[s];
-                    if (sz == 1) {
-                        codes[s] = ~b0[s];
-                        small.push_back(SmallTree{b0[s], e0[s], -1, 1 - parity});
-                    } else if (sz > kSmallMax) {
-                        codes[s] = next_id++;
-                        next.push_back(LargeNode{b0[s], e0[s], codes[s], 0});
-                    } else {
-                        codes[s] = next_id;
-                        small.push_back(SmallTree{b0[s], e0[s], next_id, 1 - parity});
-                        next_id += sz - 1;
-                    }
-                }
-                fix.push_back(make_int2(nd.id, 0));
-                fix.push_back(make_int2(codes[0], codes[1]));
-            }
-            level.swap(next);
-            parity = 1 - parity;
-        }
-        // a large level's node ids were handed out before the small subtrees that follow it, so the
-        // subtrees' ranges [id, id + size - 1) and the large ids never overlap (the total is n - 1)
-        if (!fix.empty()) {
-            alloc((void**)&d_fix, sizeof(int2) * fix.size());
-            if (err != hipSuccess) goto done;
-            if ((err = hipMemcpyAsync(d_fix, fix.data(), sizeof(int2) * fix.size(), hipMemcpyHostToDevice, stream)) !=
-                hipSuccess)
-                goto done;
-            const int nf = (int)fix.size() / 2;
-            hipLaunchKernelGGL(k_sah_fix, dim3((nf + 255) / 256), dim3(256), 0, stream, d_fix, nf, child);
-            if ((err = hipGetLastError()) != hipSuccess) goto done;
-        }
-        if (!small.empty()) {
-            alloc((void**)&d_small, sizeof(SmallTree) * small.size());
-            if (err != hipSuccess) goto done;
-            if ((err = hipMemcpyAsync(d_small, small.data(), sizeof(SmallTree) * small.size(), hipMemcpyHostToDevice,
-                                      stream)) != hipSuccess)
-                goto done;
-            const int nt = (int)small.size();
-            hipLaunchKernelGGL(k_sah_small, dim3((nt + kSmallWaves - 1) / kSmallWaves), dim3(kSmallBlock), 0, stream, T,
-                               O, d_small, nt, buf[0], buf[1]);
-            if ((err = hipGetLastError()) != hipSuccess) goto done;
-        }
-        err = hipStreamSynchronize(stream);
+    if (!small.empty()) {
+        if ((err = d_small.alloc(small.size())) != hipSuccess) return err;
+        if ((err = hipMemcpyAsync(d_small, small.data(), sizeof(SmallTree) * small.size(), hipMemcpyHostToDevice,
+                                  stream)) != hipSuccess)
+            return err;
+        const int nt = (int)small.size();
+        hipLaunchKernelGGL(k_sah_small, dim3((nt + kSmallWaves - 1) / kSmallWaves), dim3(kSmallBlock), 0, stream, T, O,
+                           d_small.get(), nt, D.buf[0].get(), D.buf[1].get());
+        if ((err = hipGetLastError()) != hipSuccess) return err;
     }
-done:
-    (void)hipStreamSynchronize(stream);
-    for (void* p : {(void*)tlo, (void*)thi, (void*)cen, (void*)buf[0], (void*)buf[1], (void*)d_large, (void*)d_small,
-                    (void*)d_mid, (void*)d_fix, (void*)d_chunks, (void*)d_acc, (void*)d_bins, (void*)d_code,
-                    (void*)d_cleft})
-        if (p) (void)hipFree(p);
-    return err;
+    return hipStreamSynchronize(stream);
 }
 
 }  // namespace pt

@@ -1489,52 +1489,55 @@ hipError_t launch_shade_mode(int mode, bool fused, const DevScene& S, const DevL
 
 }  // namespace
 
-size_t wavefront_bytes(int paths, int max_bounces) {
-    size_t P = (size_t)paths;
-    return P * sizeof(float4) * (4 /*rays x2 queues*/ + 1 /*hit*/ + 3 /*beta x2, L*/ + 3 /*shadow*/) +
-           P * (2 + kNeeRegions + kShadeBuckets) * sizeof(int) + count_bytes(max_bounces);
-}
+namespace {
 
-hipError_t wavefront_alloc(WFState& W, int paths, int max_bounces) {
-    size_t P = (size_t)paths;
-    hipError_t e = hipSuccess;
-    auto al = [&](void** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes > 0 ? bytes : 16);
-    };
-    al((void**)&W.ray_o[0], P * sizeof(float4));
-    al((void**)&W.ray_o[1], P * sizeof(float4));
-    al((void**)&W.ray_d[0], P * sizeof(float4));
-    al((void**)&W.ray_d[1], P * sizeof(float4));
-    al((void**)&W.hit, P * sizeof(float4));
-    al((void**)&W.beta, P * sizeof(float4));
-    al((void**)&W.beta_q, P * sizeof(float4));
-    al((void**)&W.L, P * sizeof(float4));
-    al((void**)&W.sh_o, P * sizeof(float4));
-    al((void**)&W.sh_d, P * sizeof(float4));
-    al((void**)&W.sh_c, P * sizeof(float4));
-    al((void**)&W.aux, P * sizeof(int));
-    al((void**)&W.vis, P * sizeof(int));
-    al((void**)&W.nq, P * kNeeRegions * sizeof(int));
-    al((void**)&W.sq, P * kShadeBuckets * sizeof(int));
-    al((void**)&W.count, count_bytes(max_bounces));
-    if (e != hipSuccess) {
-        // no partial queue set survives a failed allocation: paths stays 0, so the next
-        // launch_frames allocates again instead of launching on null queues
-        wavefront_free(W);
-        (void)hipGetLastError();
-        return e;
+// The queue set's arrays: where each lives in WFState, its element size and its elements per path
+// (0: `count`, which count_bytes(max_bounces) sizes).
+struct QueueArray {
+    void** (*slot)(WFState&);
+    size_t elem, per_path;
+    size_t bytes(size_t paths, int max_bounces) const {
+        return per_path ? paths * per_path * elem : count_bytes(max_bounces);
     }
-    W.paths = paths;
-    W.max_bounces = max_bounces;
-    return e;
+};
+#define PT_QUEUE(member, per_path) \
+    QueueArray { [](WFState& W) { return (void**)&W.member; }, sizeof(*WFState().member), per_path }
+const QueueArray kQueueArrays[] = {
+    PT_QUEUE(ray_o[0], 1), PT_QUEUE(ray_o[1], 1), PT_QUEUE(ray_d[0], 1), PT_QUEUE(ray_d[1], 1),
+    PT_QUEUE(hit, 1),      PT_QUEUE(beta, 1),     PT_QUEUE(beta_q, 1),   PT_QUEUE(L, 1),
+    PT_QUEUE(sh_o, 1),     PT_QUEUE(sh_d, 1),     PT_QUEUE(sh_c, 1),     PT_QUEUE(aux, 1),
+    PT_QUEUE(vis, 1),      PT_QUEUE(nq, kNeeRegions), PT_QUEUE(sq, kShadeBuckets), PT_QUEUE(count, 0)};
+#undef PT_QUEUE
+
+}  // namespace
+
+size_t wavefront_bytes(int paths, int max_bounces) {
+    size_t b = 0;
+    for (const QueueArray& a : kQueueArrays) b += a.bytes((size_t)paths, max_bounces);
+    return b;
 }
 
-void wavefront_free(WFState& W) {
-    void* ps[] = {W.ray_o[0], W.ray_o[1], W.ray_d[0], W.ray_d[1], W.hit, W.beta, W.beta_q, W.L, W.sh_o, W.sh_d, W.sh_c,
-                  W.aux, W.vis, W.nq, W.sq, W.count};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    W = WFState{};
+hipError_t WFQueues::alloc(int paths, int max_bounces) {
+    release();
+    for (const QueueArray& a : kQueueArrays) {
+        const size_t bytes = a.bytes((size_t)paths, max_bounces);
+        const hipError_t e = hipMalloc(a.slot(w_), bytes > 0 ? bytes : 16);
+        if (e != hipSuccess) {
+            *a.slot(w_) = nullptr;
+            release();
+            (void)hipGetLastError();
+            return e;
+        }
+    }
+    w_.paths = paths;
+    w_.max_bounces = max_bounces;
+    return hipSuccess;
+}
+
+void WFQueues::release() {
+    for (const QueueArray& a : kQueueArrays)
+        if (*a.slot(w_)) (void)hipFree(*a.slot(w_));
+    w_ = WFState{};
 }
 
 hipError_t launch_wavefront_batch(const DevScene& S, const DevLaunch& L, const WFState& W, const WFBatch& B) {

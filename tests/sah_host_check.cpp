@@ -1,7 +1,7 @@
 // Host check of the binned-SAH builder and its insertion-based refinement (pt_sah.cpp), built by
 // tests/test_sah_host.py with hipcc --cuda-host-only (no GPU).  Reads float4 triangles (three
 // vertices each, w ignored) from argv[1], builds the binary tree, refines it with argv[2] rounds
-// and checks both trees against the layout lbvh_build consumes:
+// and checks both trees against the layout bvh_build consumes:
 //   - order is a permutation of the triangles;
 //   - every internal node but the root and every leaf is some node's child exactly once;
 //   - a node's leaf range is its first child's followed directly by its second child's;
@@ -107,7 +107,7 @@ int main(int argc, char** argv) {
     if (std::fread(tri.data(), sizeof(float4), tri.size(), f) != tri.size()) return 2;
     std::fclose(f);
     const int n = (int)(tri.size() / 3), rounds = std::atoi(argv[2]);
-    if (n < 2) return 2;  // lbvh_build takes the SAH branch for n > 1 only
+    if (n < 2) return 2;  // bvh_build takes the SAH branch for n > 1 only
     std::vector<uint32_t> order;
     std::vector<int2> child, range;
     std::vector<float4> box;

@@ -1,5 +1,5 @@
 """Host checks of the binned-SAH builder and its insertion-based refinement (pt_sah.cpp, the
-default `PT_BVH_SAH` / `PT_BVH_AUTO` tree that lbvh_build hands to the GPU collapse; replaces
+default `PT_BVH_SAH` / `PT_BVH_AUTO` tree that bvh_build hands to the GPU collapse; replaces
 optixAccelBuild, OptixRenderer.cpp:306-456).  tests/sah_host_check.cpp is compiled host-only and
 checks the tree layout before and after `sah_reinsert` on triangle soups, degenerate and NaN
 triangles and the Sponza-class scene.  The images these trees give are checked bit for bit on
@@ -81,7 +81,7 @@ def test_degenerate_coincident_and_nan(checker, tmp_path):
 
 def test_sponza_class_refinement_passes_the_gate(checker, tmp_path):
     """The Sponza-class scene: the refinement cuts the binary cost by well over the 2 % that
-    lbvh_build requires before it keeps the refined tree (8.9 % when measured)."""
+    bvh_build requires before it keeps the refined tree (8.9 % when measured)."""
     from optixpathtracer_amd import scenes
 
     sc = scenes.sponza_class()
