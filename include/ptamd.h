@@ -135,9 +135,9 @@ typedef struct pt_stats {
     uint64_t trace_kernel_bytes; /* their algorithmic queue bytes: 32 B per ray read + 16 B per
                                     hit / shadow record written (k_extend with primary dedup
                                     writes one record per frame of the batch) */
-    uint64_t strict_retraces;    /* rays traced a second time because their first answer was a hit
-                                    outside the triangle's own box (pt_device.h tri_accept; counted
-                                    while pt_set_traversal_stats(r, 1)) */
+    uint64_t strict_retraces;    /* always 0: no traversal traces a ray twice any more (every candidate
+                                    hit is held to pt_device.h tri_accept_in as it is met); the field
+                                    keeps the struct's layout */
     /* wave schedule of the lane-refilling trace kernels (k_extend, k_trace_pair),
        counted while pt_set_traversal_stats(r, 1): loop iterations of the waves, lanes with a ray
        in flight summed over them, iterations that ran the node half / the triangle half of the
@@ -486,7 +486,8 @@ int pt_camera_from_blender(const float blender_position[3], const float blender_
                            float inverse_view[16], float inverse_projection[16]);
 
 /* Debug / parity: trace n rays (origin xyz, dir xyz, tmin, tmax per ray = 8 floats) against
- * the LBVH.  prim = global triangle index (meshes concatenated) or -1. */
+ * the renderer's BVH, whichever builder made it, with the per-lane traversal kernel (k_trace).
+ * prim = global triangle index (meshes concatenated) or -1. */
 int pt_trace_rays(pt_renderer* r, const float* host_rays, int32_t n, int32_t* prim, float* t,
                   float* u, float* v, int32_t* backface, int32_t any_hit);
 

@@ -3,7 +3,7 @@
 //
 // k_gbuffer: one thread per pixel, tiled like k_render_mega (a 256-thread workgroup covers 16x16
 // pixels, each wave64 an 8x8 quadrant).  The pixel's unjittered camera ray is traced over the
-// radiance ray's interval with the same strict re-trace rule and alpha cut-out, and the hit is
+// radiance ray's interval with the same acceptance rule (tri_accept_in) and alpha cut-out, and the hit is
 // reconstructed as the first bounce of a path reconstructs it: what it writes equals the debug
 // record of that bounce bit for bit; the hit's barycentrics and primitive go into a guide record of
 // their own for the motion vectors of pt_temporal.hip.  No queues, no random numbers.

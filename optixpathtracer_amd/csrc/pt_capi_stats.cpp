@@ -124,7 +124,7 @@ int pt_get_stats(pt_renderer* r, pt_stats* out) {
     out->shadow_rays = c[kCtrShadowRays];
     out->trace_kernel_rays = c[kCtrTraceRays];
     out->trace_kernel_bytes = c[kCtrTraceBytes];
-    out->strict_retraces = c[kCtrRetraces];
+    out->strict_retraces = 0;  // no traversal re-traces any more (pt_device.h tri_accept_in); ABI field
     out->wave_steps = c[kCtrWaveSteps];
     out->wave_active_lanes = c[kCtrWaveActive];
     out->wave_node_steps = c[kCtrWaveNodeSteps];

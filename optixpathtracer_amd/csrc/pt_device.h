@@ -140,7 +140,7 @@ enum Counter : int {
     kCtrShadowRays,      // shadow rays
     kCtrTraceRays,       // rays of the timed trace kernels (k_extend, k_trace_pair)
     kCtrTraceBytes,      // their algorithmic queue bytes
-    kCtrRetraces,        // strict re-traces
+    kCtrRetired9,        // unused (was the strict re-trace count); the later slots keep their numbers
     // wave schedule of the trace kernels (pt_stats wave_*; shader cycles under PT_CYCLE_PROBE)
     kCtrWaveSteps,
     kCtrWaveActive,
@@ -203,7 +203,7 @@ __device__ __forceinline__ uint64_t probe_clock(const T& dep) {  // once `dep` i
 }
 
 struct TravStats {
-    uint32_t nodes = 0, tris = 0, rays = 0, overflow = 0, retrace = 0;
+    uint32_t nodes = 0, tris = 0, rays = 0, overflow = 0;
     uint32_t lds_nodes = 0;  // node visits served from the staged top levels (stage_top_nodes)
     uint32_t unocc = 0;      // k_trace_pair: shadow rays that found their light unoccluded
     uint32_t skips = 0;      // k_trace_pair: extension rays that carried a skip link (pt_skip.h)
@@ -232,7 +232,7 @@ template <bool STATS>
 __device__ __forceinline__ void flush_trav_stats(unsigned long long* counters, const TravStats& ts) {
     if (!STATS || !counters) return;
     const unsigned long long a = wave_sum_u64(ts.nodes), c = wave_sum_u64(ts.tris), d = wave_sum_u64(ts.rays);
-    const unsigned long long e = wave_sum_u64(ts.overflow), r = wave_sum_u64(ts.retrace);
+    const unsigned long long e = wave_sum_u64(ts.overflow);
     const unsigned long long l = wave_sum_u64(ts.lds_nodes), u = wave_sum_u64(ts.unocc);
     const unsigned long long sk = wave_sum_u64(ts.skips);
     if ((threadIdx.x & 63) == 0) {  // the wave-schedule counts are kept by every lane alike: lane 0's
@@ -240,7 +240,6 @@ __device__ __forceinline__ void flush_trav_stats(unsigned long long* counters, c
         atomicAdd(&counters[kCtrTriTests], c);
         atomicAdd(&counters[kCtrRays], d);
         atomicAdd(&counters[kCtrStackOverflows], e);
-        atomicAdd(&counters[kCtrRetraces], r);
         atomicAdd(&counters[kCtrWaveSteps], (unsigned long long)ts.steps);
         atomicAdd(&counters[kCtrWaveActive], (unsigned long long)ts.active);
         atomicAdd(&counters[kCtrWaveNodeSteps], (unsigned long long)ts.node_steps);
@@ -277,27 +276,39 @@ PT_HD void tri_box_padded(f3 v0, f3 e1, f3 e2, float lo[3], float hi[3]) {
     }
 }
 
-// Hit acceptance.  A Moller-Trumbore hit at t on triangle T counts only if t lies in the slab
-// interval [tn, tf] of T's padded box, with relative slack K = kSlabWiden:
-//     tn <= t*K,   t <= tf*K,   tn <= tf*K.
-// A node keeps a child box B iff max(tn_B, tmin) <= min(tf_B, best)*K (node_eval).  B contains
-// T's padded box and the slab distance is monotone in the plane coordinate, so tn_B <= tn and
-// tf_B >= tf: a box holding an acceptable hit with t <= best is never culled.  The closest hit
-// is therefore the (t, original index) minimum over the acceptable hits for ANY BVH and ANY
+// Hit acceptance.  A Moller-Trumbore hit on triangle T passes u, v (tri_test) and then has its t
+// brought into the slab interval [tn, tf] of T's padded box, with relative slack K = kSlabWiden:
+//     tn <= t*K and t <= tf*K: t stays;   t*K < tn: t = tn;   t > tf*K: t = tf
+// (the ray must pass the box, tn <= tf*K, and t be finite).  The caller then asks tmin <= t <= best.
+// The true hit lies in T, hence in the box; a grazing hit's fp32 t can be off by more than any fixed
+// slack, and dropping it instead let rays through slivers ("The rule against float64
+// geometry").  A node keeps a child box B iff max(tn_B, tmin) <= min(tf_B, best)*K (node_eval).  B
+// contains T's padded box and the slab distance is monotone in the plane coordinate, so tn_B <= tn
+// and tf_B >= tf: a box holding an accepted hit with t <= best is never culled.  The closest hit
+// is therefore the (t, original index) minimum over the accepted hits for ANY BVH and ANY
 // visiting order -- the oracle's binary median-split BVH and this BVH4 give the same answer.
 // Without the rule (round 1), a grazing ray could be accepted by Moller-Trumbore at a point
 // outside the triangle's own box (barycentric rounding at cos = 0.038), whose box the cull then
 // dropped or kept depending on which triangle had set `best` first -- a visiting-order, hence
 // wave-neighbour, dependence ("Closest-hit determinism").
-__device__ __forceinline__ bool tri_accept(const float4 A, const float4 E1, const float4 E2, f3 inv, f3 io, float t) {
+__device__ __forceinline__ bool tri_accept(const float4 A, const float4 E1, const float4 E2, f3 inv, f3 io, float& t) {
     float lo[3], hi[3];
     tri_box_padded(mk(A.x, A.y, A.z), mk(E1.x, E1.y, E1.z), mk(E2.x, E2.y, E2.z), lo, hi);
     const float ax = __fmaf_rn(lo[0], inv.x, -io.x), bx = __fmaf_rn(hi[0], inv.x, -io.x);
     const float ay = __fmaf_rn(lo[1], inv.y, -io.y), by = __fmaf_rn(hi[1], inv.y, -io.y);
     const float az = __fmaf_rn(lo[2], inv.z, -io.z), bz = __fmaf_rn(hi[2], inv.z, -io.z);
     const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
-    const float tfk = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)) * kSlabWiden;
-    return tn <= t * kSlabWiden && t <= tfk && tn <= tfk;
+    const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+    const float tfk = tf * kSlabWiden;
+    const bool ok = (tn <= tfk) & (fabsf(t) <= 3.4028235e38f);
+    t = !(tn <= t * kSlabWiden) ? tn : (!(t <= tfk) ? tf : t);
+    return ok;
+}
+// tri_accept, then the ray's interval on the accepted t.
+__device__ __forceinline__ bool tri_accept_in(const float4 A, const float4 E1, const float4 E2, f3 inv, f3 io, float tmin,
+                                              float tmax, float& t) {
+    const bool ok = tri_accept(A, E1, E2, inv, io, t);
+    return ok & (t >= tmin && t <= tmax);
 }
 
 __device__ __forceinline__ void cswap(float& ta, int& ca, float& tb, int& cb) {
@@ -409,10 +420,8 @@ struct TravRay {
     int leaf;          // leaf whose triangles are tested alongside node steps
     int nx, ny, nz;    // byte offset (0 or 16) of the near slab plane per axis within the node
     bool any;          // any-hit ray (only read by kRayMixed traversals)
-    bool strict;       // re-trace: only acceptable hits are taken (trav_restart_strict)
     int path;          // wavefront rays: the path id (closest hit) or the carried word (any hit) for
                        // finish; per-lane any-hit rays: the bits of the hit's t once they stop
-                       // (trav_result_ok)
     int skip;          // kRayMixedSkip traversals: the child link this ray drops unvisited (pt_skip.h),
                        // kEmptyChild = none
 };
@@ -440,7 +449,6 @@ __device__ __forceinline__ void trav_init(TravRay& s, f3 o, f3 d, float tmin, fl
     s.spc = 0;
     s.leaf = kEmptyChild;
     s.any = false;
-    s.strict = false;
     s.skip = kEmptyChild;
 }
 __device__ __forceinline__ void trav_init(TravState& s, f3 o, f3 d, float tmin, float tmax) {
@@ -455,11 +463,11 @@ __device__ __forceinline__ bool is_any(const TravRay& s) {
 }
 
 // Moller-Trumbore; OptiX barycentric convention (u weights v1, v weights v2); closed
-// interval [tmin, tmax]; det < 0 <=> back face (ray along the CCW normal).  Same
+// intervals; no test of t (tri_accept_in clamps it first); det < 0 <=> back face (ray along the CCW normal).  Same
 // arithmetic order and NaN behaviour as the oracle's tri_hit (edges precomputed with the
 // same subtraction); predicated instead of early exits (no divergent branches per test).
-__device__ __forceinline__ bool tri_test(const float4 A, const float4 E1, const float4 E2, f3 o, f3 d, float tmin,
-                                         float tmax, float& th, float& uh, float& vh, bool& back) {
+__device__ __forceinline__ bool tri_test(const float4 A, const float4 E1, const float4 E2, f3 o, f3 d, float& th,
+                                         float& uh, float& vh, bool& back) {
     f3 v0 = mk(A.x, A.y, A.z), e1 = mk(E1.x, E1.y, E1.z), e2 = mk(E2.x, E2.y, E2.z);
     f3 p = cross(d, e2);
     float det = dot(e1, p);
@@ -473,7 +481,7 @@ __device__ __forceinline__ bool tri_test(const float4 A, const float4 E1, const 
     uh = u;
     vh = v;
     back = det < 0.0f;
-    return (det != 0.0f) & !(u < 0.0f || u > 1.0f) & !(v < 0.0f || u + v > 1.0f) & (t >= tmin && t <= tmax);
+    return (det != 0.0f) & !(u < 0.0f || u > 1.0f) & !(v < 0.0f || u + v > 1.0f);
 }
 
 // Move the bottom (DEPTH / 2) LDS entries to the spill array (rare).  pt_create bounds the
@@ -602,9 +610,9 @@ __device__ __forceinline__ void node_eval(const NodeLoad& n, const TravRay& s, f
 }
 
 // Test one triangle of the leaf s.leaf and advance it; true when an any-hit ray is done.
-// Closest-hit lanes take a hit by the (t, original index) order; in strict mode
-// (trav_restart_strict) only acceptable hits count.  Any-hit lanes stop at the first hit and
-// record only h.tri.
+// Closest-hit lanes take a hit by the (t, original index) order; only accepted hits count
+// (tri_accept_in: t clamped into the triangle's slab interval, then inside [tmin, best]).  Any-hit
+// lanes stop at the first hit and record only h.tri.
 template <int ANY, bool STATS, bool TEX>
 __device__ __forceinline__ bool leaf_tri_eval(const DevScene& S, TravState& s, TravStats& ts, const float4 A,
                                               const float4 E1, const float4 E2) {
@@ -613,9 +621,10 @@ __device__ __forceinline__ bool leaf_tri_eval(const DevScene& S, TravState& s, T
     if (STATS) ts.tris++;
     float t, u, v;
     bool bk;
-    bool hit = tri_test(A, E1, E2, s.o, s.d, s.tmin, s.best, t, u, v, bk);
+    bool hit = tri_test(A, E1, E2, s.o, s.d, t, u, v, bk);
+    if (hit) hit = tri_accept_in(A, E1, E2, s.inv, s.io, s.tmin, s.best, t);
+    // after the acceptance: both only remove hits, and the texture fetch runs for accepted hits only
     if (TEX && hit && __float_as_int(E2.w) != 0) hit = !alpha_cut(S, ti, __float_as_int(E1.w), u, v);
-    if (s.strict && hit) hit = tri_accept(A, E1, E2, s.inv, s.io, t);  // rare re-trace lanes only
     const int oi = __float_as_int(A.w);
     s.leaf = cnt > 1 ? ~(((first + 1) << 3) | (cnt - 2)) : kEmptyChild;  // rest of the leaf
     if (is_any<ANY>(s)) {
@@ -795,19 +804,19 @@ __device__ __forceinline__ bool wave_tri_batch(const DevScene& S, TravRay& s, bo
         float t, u, v;
         if (STATS && valid) ts.tris++;
         const float4 A = S.isect[3 * ti], E1 = S.isect[3 * ti + 1], E2 = S.isect[3 * ti + 2];
-        bool hit = tri_test(A, E1, E2, o, d, 0.0f, tmax, t, u, v, bk) && valid;
-        if (TEX && hit && __float_as_int(E2.w) != 0) hit = !alpha_cut(S, ti, __float_as_int(E1.w), u, v);
+        bool hit = tri_test(A, E1, E2, o, d, t, u, v, bk) && valid;
         const int oi = __float_as_int(A.w);
-        // Every candidate is held to the acceptance rule here (tri_accept with the owner's inv / io,
-        // read across lanes by the whole wave), so the batch only ever takes acceptable hits: the
-        // traversal is strict from the start and its finished rays need no check and no re-trace.
+        // Every candidate is held to the acceptance rule here (tri_accept_in with the owner's inv / io,
+        // read across lanes by the whole wave), so the batch only ever takes accepted hits: the
+        // finished rays need no further check.
         // (Round 2 checked the finished rays' hits in the trace loop's refill block instead, which
         // loaded each hit triangle again and stalled the block: +3.3 % Lambert)
         if (__ballot(hit)) {  // wave-uniform
             const f3 inv = mk(__shfl(s.inv.x, owner, 64), __shfl(s.inv.y, owner, 64), __shfl(s.inv.z, owner, 64));
             const f3 io = mk(__shfl(s.io.x, owner, 64), __shfl(s.io.y, owner, 64), __shfl(s.io.z, owner, 64));
-            if (hit) hit = tri_accept(A, E1, E2, inv, io, t);
+            if (hit) hit = tri_accept_in(A, E1, E2, inv, io, 0.0f, tmax, t);
         }
+        if (TEX && hit && __float_as_int(E2.w) != 0) hit = !alpha_cut(S, ti, __float_as_int(E1.w), u, v);
         // t >= tmin = 0: with the sign bit cleared (t = -0), its bits order as an unsigned integer
         const unsigned long long key =
             ((unsigned long long)(__float_as_uint(t) & 0x7fffffffu) << 32) | (unsigned long long)(uint32_t)oi;
@@ -877,41 +886,11 @@ __device__ __forceinline__ bool trav_node_step(const DevScene& S, TravRay& s, in
     return s.cur == kEmptyChild && s.leaf == kEmptyChild;
 }
 
-// Per-lane traversals (trav_step: the megakernel and k_trace; the wavefront's triangle batches
-// are strict throughout): a finished traversal's answer stands unless its hit is not acceptable
-// (tri_accept) -- then the ray is traced again in strict mode.  If the final hit is acceptable it IS the minimum
-// over the acceptable hits: every acceptable hit ordered before it had t <= best throughout,
-// so its boxes were never culled and it was tested and taken.  It runs once per finished ray,
-// on the hit's t kept by the traversal and the hit triangle's record (A, E1, E2).
-template <int ANY>
-__device__ __forceinline__ bool trav_hit_acceptable(const TravState& s, const float4 A, const float4 E1,
-                                                    const float4 E2) {
-    const float t = is_any<ANY>(s) ? __int_as_float(s.path) : s.h.t;
-    return tri_accept(A, E1, E2, s.inv, s.io, t);
-}
-template <int ANY, bool TEX>
-__device__ __forceinline__ bool trav_result_ok(const DevScene& S, const TravState& s) {
-    if (s.strict || s.h.tri < 0) return true;
-    const int ti = s.h.tri;
-    return trav_hit_acceptable<ANY>(s, S.isect[3 * ti], S.isect[3 * ti + 1], S.isect[3 * ti + 2]);
-}
-
-// Trace the ray again from the root, taking acceptable hits only.  Closest-hit lanes restart
-// from tmax_closest; any-hit lanes keep their tmax (best never shrinks for them) and their
-// carried fields.
-template <int ANY>
-__device__ __forceinline__ void trav_restart_strict(TravState& s, float tmax_closest) {
-    s.cur = 0;
-    s.sp = 0;
-    s.spc = 0;
-    s.leaf = kEmptyChild;
-    s.strict = true;
-    s.h.tri = -1;
-    if (!is_any<ANY>(s)) {
-        s.best = tmax_closest;
-        s.h.orig = 0x7fffffff;
-    }
-}
+// Per-lane traversals (trav_step: the megakernel and k_trace) hold every candidate to tri_accept_in
+// in leaf_tri_eval, like the wavefront's triangle batches, so a finished traversal's answer stands.
+// (Before t was clamped they checked only the finished hit and traced the rare unacceptable one
+// again; under the clamp that is not enough: a hit whose Moller-Trumbore t lies past `best` may be
+// clamped to a t before it.)
 
 // Whole traversal of one ray (megakernel, k_trace).
 template <int ANY, bool STATS, int DEPTH, bool TEX>
@@ -922,12 +901,7 @@ __device__ __forceinline__ bool traverse(const DevScene& S, f3 o, f3 d, float tm
     trav_init(s, o, d, tmin, tmax);
     if (S.ntri > 0) {
         int spill[kSpillDepth];
-        while (true) {
-            while (!trav_step<ANY, STATS, DEPTH, TEX>(S, s, stk, stride, spill, ts)) {
-            }
-            if (trav_result_ok<ANY, TEX>(S, s)) break;
-            if (STATS) ts.retrace++;
-            trav_restart_strict<ANY>(s, tmax);
+        while (!trav_step<ANY, STATS, DEPTH, TEX>(S, s, stk, stride, spill, ts)) {
         }
     }
     h = s.h;

@@ -39,8 +39,9 @@
 //     cell border (lit_cell_index scales by a power of two, exactly; only fu + fv > 1 rounds) and
 //     of the ray itself, together below 2e-4 (kDarkEta below counts them); a border point may land
 //     in the neighbouring cell, whose pyramid grown by m still contains it;
-//   * the tracer's acceptance (pt_device.h tri_accept, kSlabWiden): a hit counts only with its
-//     point inside U's padded box stretched by t * 2^-12 along the ray.  t passed t <= tmax =
+//   * the tracer's acceptance (pt_device.h tri_accept_in, kSlabWiden): a hit counts only with its
+//     point inside U's padded box stretched by t * 2^-12 along the ray (a t outside that is clamped
+//     to the box's own interval, which lies inside it).  t passed t <= tmax =
 //     |l - p| <= reach, and the hit lies in the scene box like the origin (within 1e-3), so
 //     t <= min(reach, diag) + 2e-3; the factor 1.01 rounds the bound up over the fp32 rounding of
 //     t and tmax (a few 1e-7 relative).  The stretch is taken once: lit_margin(diag) took it four
@@ -77,7 +78,8 @@
 //       every ideal ray of the bundle hits inside the same region;
 //   (e) g - eta >= 2^-12 * Tmax and 2^-20 * (R / (g - eta) + 1 / cb) / aspect <= 2^-13, with
 //       Tmax = max_i |l' - c_i'| and R = the largest distance from a corner of P' to a vertex of U.
-// Why these suffice for fp32 tri_test + tri_accept (pt_device.h), with e = 2^-24:
+// Why these suffice for fp32 tri_test + tri_accept_in (pt_device.h), with e = 2^-24.  They show that
+// t passes unclamped and inside (0, tmax); tri_accept_in leaves such a t as it is:
 //   * u, v: tri_test forms u = (tv . (d x e2)) / det, det = e1 . (d x e2) = +-A cos.  Six roundings
 //     reach the numerator (tv, the cross product, the dot product), each <= e |tv| |e2|, and the
 //     same count reaches det relative to |e1| |e2|; with |e2| / A <= 1 / hmin and |u| <= 1 the error

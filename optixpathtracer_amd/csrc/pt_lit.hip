@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kLitBlock) void k_lit_build(DevScene S, const uint3
 
 // The occluder candidate table: one int per (light, cell), laid out light * cells + cell,
 // -1 or the leaf-order index of a triangle that probably occludes the cell's shadow rays.  It is a
-// hint: the shading kernels test the named triangle with the tracer's own tri_test + tri_accept on the
+// hint: the shading kernels test the named triangle with the tracer's own tri_test + tri_accept_in on the
 // very ray they would emit, and a passing test is the tracer's "occluded" for ANY triangle (the BVH's
 // boxes hold the triangle's padded box, so the any-hit walk reaches it or stops earlier at another
 // hit).  A wrong or stale entry costs speed only; the one invariant is -1 <= entry < ntri.

@@ -15,10 +15,11 @@
 // lanes drop the named link when it turns up in TravState::cur (trav_node_step).
 //
 // Why the images do not change.  The wavefront's closest hit is the (t, original index) minimum over
-// the hits that fp32 tri_test + tri_accept take (pt_device.h), whatever the visiting order, so leaving
-// out triangles that can produce no such hit leaves every hit record as it was; tri_accept and the
-// alpha cut-outs of the textured kernels only remove hits.  With h(x) the height over T's plane on the
-// ray's side (n the unit normal, exact arithmetic):
+// the hits that fp32 tri_test + tri_accept_in take (pt_device.h), whatever the visiting order, so leaving
+// out triangles that can produce no such hit leaves every hit record as it was; tri_accept_in's box
+// and range tests and the alpha cut-outs of the textured kernels only remove hits.  Its clamp does
+// not: it can turn a t outside [0, best] into one inside, which "the clamped t" below deals with.
+// With h(x) the height over T's plane on the ray's side (n the unit normal, exact arithmetic):
 //   * the ray.  p is the fp32 combination of T's vertices with accepted (u, v), off = +-1e-3 * Ng, and
 //     tri_test subtracts v0 from o once more: together below 6e-5 of position error for coordinates up
 //     to kLitMaxCoord = 128 (ulp 7.6e-6), counted as a shift of the whole ray.  T's fp32 normal is
@@ -42,6 +43,18 @@
 //     them needs mu <= 96 e (Lmax + R) / (hmin |cos|) + 5 e.  Against mu >= 4.4e-4 / s that is
 //     impossible for |cos| >= 0.013 s (Lmax + R) / hmin: on the benchmark's spheres (s <= 0.04,
 //     Lmax + R <= 0.45, hmin >= 0.007 at the poles) for every ray more than 2 degrees off U's plane.
+//   * the clamped t.  The bullets above exclude a pass of (u, v) with t >= 0.  A pass with t < 0 used to
+//     end at tri_test's own range test; now the range test follows tri_accept's clamp, and U's
+//     axis-aligned box may well cross T's plane, so its slab interval [tn, tf] can reach past 0.  Take a
+//     U below T whose fp32 (u, v) pass, under the premise of the last bullet (|cos| above its bound).
+//     In exact arithmetic the ray's line then meets U itself (were the exact (u, v) outside by mu, the
+//     point would be mu Lmax beside U, and the same argument runs with that many units of slack); the
+//     point's height is <= kLitDelta, so by the heights t_exact <= -4.4e-4 / (d . n) <= -4.4e-4.
+//     (i) The point lies in U, hence in U's padded box, so tn <= t_exact: tn is negative, and a t
+//     clamped up to tn fails 0 <= t.  (ii) The fp32 t differs from t_exact by a relative e (Lmax + R) /
+//     (hmin |cos|) times a small count, far below 1 under the premise, so it is negative too: left
+//     unclamped it fails 0 <= t, and it can never exceed tf K with tf >= 0, which a t clamped down to an
+//     accepted tf would need.  So no t of a U below T, clamped or not, passes the range test.
 //   * what is assumed.  For a ray closer to U's plane than that bound the worst-case rounding above no
 //     longer excludes a hit, although the ray stays 4.4e-4 -- 58 ulps of the largest coordinate, about
 //     2000 of the benchmark's -- away from every point of U.  This is the premise the lit table's

@@ -698,8 +698,8 @@ __device__ __forceinline__ void lit_count_block(const DevLaunch& L, const int* l
 }
 // The occluder candidate table (pt_lit.hip k_occ_build): `t` = the entry light * cells + cell of a
 // shadow ray the lit table left open (its origin is offset to the light's side of a triangle with
-// cells), -1 or a triangle.  True: the candidate passes the tracer's own test on this very ray -- tri_test with tmin 0 and the
-// ray's tmax, then tri_accept with inv and io formed as trav_init forms them -- so k_trace_pair /
+// cells), -1 or a triangle.  True: the candidate passes the tracer's own test on this very ray -- tri_test, then tri_accept_in
+// with tmin 0, the ray's tmax, and inv and io formed as trav_init forms them -- so k_trace_pair /
 // k_shadow_vis would answer "occluded": they reach that triangle (every BVH box that holds it
 // contains its padded box) or stop earlier at another hit.  That holds for ANY entry, so a stale or
 // wrong one only costs the test.  A cut-out triangle (E2.w != 0, alpha_cut may drop its hits in the
@@ -710,10 +710,10 @@ __device__ __forceinline__ bool occ_answers(const DevScene& S, int t, f3 o, f3 d
     const float4 A = S.isect[3 * t], E1 = S.isect[3 * t + 1], E2 = S.isect[3 * t + 2];
     float th, uh, vh;
     bool bk;
-    if (!tri_test(A, E1, E2, o, d, 0.0f, tmax, th, uh, vh, bk)) return false;
+    if (!tri_test(A, E1, E2, o, d, th, uh, vh, bk)) return false;
     if (TEX && __float_as_int(E2.w) != 0) return false;
     const f3 inv = safe_inv(d);
-    return tri_accept(A, E1, E2, inv, mk(o.x * inv.x, o.y * inv.y, o.z * inv.z), th);
+    return tri_accept_in(A, E1, E2, inv, mk(o.x * inv.x, o.y * inv.y, o.z * inv.z), 0.0f, tmax, th);
 }
 
 // The skip table (pt_skip.h) in the fused shading kernels.  kSkipCode: the material modes whose kernels

@@ -1021,8 +1021,9 @@ static int alpha_cut(const orc_scene* s, int t, float u, float v) {
 /* ---- Closest-hit rule shared with the kernels (pt_device.h tri_accept / node_eval) ------
  * OptiX's closest hit comes from closed code (devicePrograms.cu:243-260); this restatement
  * defines it as the (t, global index) minimum over the ACCEPTABLE Moller-Trumbore hits: the
- * hit's t must lie in the slab interval of the triangle's own padded box, with relative slack
- * K = 1 + 2^-12.  The box uses the vertices as the hit test sees them (v0, v0 + e1, v0 + e2);
+ * hit's t is brought into the slab interval of the triangle's own padded box (left alone within the
+ * relative slack K = 1 + 2^-12, else clamped to the interval's near or far end) and must then lie
+ * in [tmin, best].  The box uses the vertices as the hit test sees them (v0, v0 + e1, v0 + e2);
  * slab distances are fmaf(plane, inv, -o*inv) with inv = 1/d (a zero component -> +-1e30).
  * Every BVH box below is a union of these boxes, and the box cull keeps a box iff
  * max(tn, tmin) <= min(tf, best) * K, so no box holding an acceptable hit with t <= best is
@@ -1065,12 +1066,20 @@ static inline void slab_interval(const float lo[3], const float hi[3], v3 inv, v
     *tn = mx(mx(mn(ax, bx), mn(ay, by)), mn(az, bz));
     *tf = mn(mn(mx(ax, bx), mx(ay, by)), mx(az, bz));
 }
-static int tri_accept(const orc_scene* s, int t, v3 inv, v3 io, float th) {
+/* The hit's t, brought into the slab interval [tn, tf] of the triangle's own padded box: a t with
+ * tn <= t K and t <= tf K stays as it is, one before the interval becomes tn, one past it tf (the true
+ * hit lies in the triangle, hence in the box: a grazing hit's t can be off by more than the slack,
+ * and dropping it let the ray through a sliver).  0 when the ray misses the box or t is not finite.
+ * The caller tests tmin <= t <= best on the result. */
+static int tri_accept(const orc_scene* s, int t, v3 inv, v3 io, float* th) {
     float lo[3], hi[3], tn, tf;
     tri_bounds(s, t, lo, hi);
     slab_interval(lo, hi, inv, io, &tn, &tf);
     float tfk = tf * kSlabWiden;
-    return tn <= th * kSlabWiden && th <= tfk && tn <= tfk;
+    if (!(tn <= tfk) || !(fabsf(*th) <= 3.4028235e38f)) return 0;
+    if (!(tn <= *th * kSlabWiden)) *th = tn;
+    else if (!(*th <= tfk)) *th = tf;
+    return 1;
 }
 static float centroid(const orc_scene* s, int t, int a) {
     float lo[3], hi[3];
@@ -1189,9 +1198,9 @@ void orc_scene_destroy(orc_scene* s) {
 }
 int32_t orc_scene_triangles(const orc_scene* s) { return s->ntri; }
 
-/* Moller-Trumbore, OptiX barycentric convention (u -> v1, v -> v2); closed interval. */
-static int tri_hit(const orc_scene* s, int t, v3 o, v3 d, float tmin, float tmax, float* th,
-                   float* uh, float* vh, int* back) {
+/* Moller-Trumbore, OptiX barycentric convention (u -> v1, v -> v2); closed interval.  No test of
+ * t: the caller clamps it into the triangle's slab interval first (tri_accept). */
+static int tri_hit(const orc_scene* s, int t, v3 o, v3 d, float* th, float* uh, float* vh, int* back) {
     v3 v0 = s->v[3 * t], v1 = s->v[3 * t + 1], v2 = s->v[3 * t + 2];
     v3 e1 = sub(v1, v0), e2 = sub(v2, v0);
     v3 p = cross3(d, e2);
@@ -1205,7 +1214,6 @@ static int tri_hit(const orc_scene* s, int t, v3 o, v3 d, float tmin, float tmax
     float v = dot3(d, q) * inv;
     if (v < 0.0f || u + v > 1.0f) return 0;
     float tt = dot3(e2, q) * inv;
-    if (!(tt >= tmin && tt <= tmax)) return 0;
     *th = tt; *uh = u; *vh = v; *back = det < 0.0f;
     return 1;
 }
@@ -1275,9 +1283,10 @@ ORC_HOT static int trace_impl(const orc_scene* s, v3 o, v3 d, float tmin, float 
                 int t = s->order[i];
                 float tt, uu, vv;
                 int bk;
-                if (!tri_hit(s, t, o, d, tmin, bt, &tt, &uu, &vv, &bk)) continue;
-                if (alpha_cut(s, t, uu, vv)) continue;  /* __anyhit__radiance/shadow */
-                if (!tri_accept(s, t, inv, io, tt)) continue;
+                if (!tri_hit(s, t, o, d, &tt, &uu, &vv, &bk)) continue;
+                if (!tri_accept(s, t, inv, io, &tt)) continue;
+                if (!(tt >= tmin && tt <= bt)) continue;
+                if (alpha_cut(s, t, uu, vv)) continue;  /* __anyhit__radiance/shadow; last: a texture fetch */
                 if (anyhit) return t;
                 if (best < 0 || tt < bt || (tt == bt && t < best)) {
                     best = t; bt = tt; bu = uu; bv = vv; bb = bk;

@@ -29,7 +29,7 @@ static float length(V3 a) { return sqrtf(dot(a, a)); }
 static float box_pad(float x) { return fabsf(x) * 9.5367431640625e-7f + 1e-6f; }
 static float ray_inv(float d) { return d != 0.0f ? 1.0f / d : copysignf(1e30f, d); }
 
-// tri_test followed by tri_accept, tmin = 0
+// tri_test followed by tri_accept_in (t clamped into the triangle's slab interval, then 0 <= t <= tmax)
 static bool tracer_hits(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float tmax) {
     const V3 p = cross(d, e2);
     const float det = dot(e1, p);
@@ -38,8 +38,8 @@ static bool tracer_hits(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float tmax) {
     const float u = dot(tv, p) * inv;
     const V3 q = cross(tv, e1);
     const float v = dot(d, q) * inv;
-    const float t = dot(e2, q) * inv;
-    const bool hit = (det != 0.0f) & !(u < 0.0f || u > 1.0f) & !(v < 0.0f || u + v > 1.0f) & (t >= 0.0f && t <= tmax);
+    float t = dot(e2, q) * inv;
+    const bool hit = (det != 0.0f) & !(u < 0.0f || u > 1.0f) & !(v < 0.0f || u + v > 1.0f);
     if (!hit) return false;
     const float a[3] = {v0.x, v0.y, v0.z}, b[3] = {e1.x, e1.y, e1.z}, c[3] = {e2.x, e2.y, e2.z};
     float lo[3], hi[3];
@@ -56,8 +56,11 @@ static bool tracer_hits(V3 v0, V3 e1, V3 e2, V3 o, V3 d, float tmax) {
     const float az = fmaf(lo[2], iv.z, -io.z), bz = fmaf(hi[2], iv.z, -io.z);
     const float K = 1.000244140625f;
     const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
-    const float tfk = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)) * K;
-    return tn <= t * K && t <= tfk && tn <= tfk;
+    const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+    const float tfk = tf * K;
+    if (!(tn <= tfk) || !(fabsf(t) <= 3.4028235e38f)) return false;
+    t = !(tn <= t * K) ? tn : (!(t <= tfk) ? tf : t);
+    return t >= 0.0f && t <= tmax;
 }
 
 // The shading kernels' shadow ray from the barycentric point (u, v) of T (reconstruct, k_shade_fused).

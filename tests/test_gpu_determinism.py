@@ -87,8 +87,36 @@ def test_shared_edge_rays_sphere_box_bit_exact():
     r = setup_renderer(sc, 32, 32, 2)
     o = OracleScene(sc)
     assert _compare(r, o, rays) > 0.9
+    # and the hits are the triangles the rays really hit: the float64 contract of tests/trace_ref.py on
+    # every second ray (2000 of them keep the exhaustive pass quick), against the device's own records
+    import trace_ref
+    import trace_scenes
+
+    sub = rays[::2]
+    tris = trace_scenes.record_triangles(r.bvh_arrays()[1])
+    trace_ref.assert_contract(tris, sub, r.trace_rays(sub), r.trace_rays(sub, any_hit=True)[0] >= 0,
+                              "gpu sphere_box shared edges")
     r.close()
     o.close()
+
+
+@pytest.mark.parametrize("far", [False, True], ids=["grazing", "far-origin"])
+def test_shared_edge_rays_sponza_meet_float64_contract(sponza, far):
+    """The Sponza-class edge rays of test_shared_edge_rays_bit_exact against float64 geometry
+    (tests/trace_ref.py), on every 32nd ray: 125 rays against 250k triangles is what a few seconds
+    buy (2000 take 40 s), and one builder is enough, since the test above pins all four to the same
+    bits.  The triangles are the device's own records."""
+    from optixpathtracer_amd.renderer import setup_renderer
+    import trace_ref
+    import trace_scenes
+
+    rays = shared_edge_rays(sponza, 4000, seed=11 + far, far=far)[::32]
+    r = setup_renderer(sponza, 32, 32, 2)
+    tris = trace_scenes.record_triangles(r.bvh_arrays()[1])
+    closest, any_hit = r.trace_rays(rays), r.trace_rays(rays, any_hit=True)[0] >= 0
+    r.close()
+    rep = trace_ref.assert_contract(tris, rays, closest, any_hit, f"gpu sponza shared edges far={far}", chunk=64)
+    assert rep.n == 125
 
 
 @pytest.mark.parametrize("scene_name", ["sphere_box_diffuse", "sponza_class"])
